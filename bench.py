@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — headline benchmark of the streaming hot path on MI355X (driver contract in the task brief).
 
-  python bench.py --gpus N --steps K --warmup W [--config C1|C2|C3|C4|C5]
+  python bench.py --gpus N --steps K --warmup W [--config C1|C2|C3|C4|C5] [--dump-outputs DIR]
   (N > 1: one rank per GPU under torch.distributed.run, as the driver launches it; typed as a bare command it starts the N ranks itself)
 
 A "step" is one pass of the hot path over one synthetic 336x336 frame stream:
@@ -70,7 +70,13 @@ def parse():
                     help="AFTER the headline measurement: STEPS more steps (default 1; 0 = off) in which the chunk captioner is the HIP 7B model itself "
                          "(one 23 k-token prefill + 128 new tokens per 40-frame chunk through llm.BatchDecoder, reference utiles.py:539-559), "
                          "reported as a separate `product` object; `value` is untouched (the metric names encode+select+retrieve+prefill)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32 / float64; large arrays as a "
+                         "fixed seeded sample), for comparing two builds output for output")
+    a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    return a
 
 
 class TimedCaptioner:
@@ -551,6 +557,86 @@ class PowerSampler:
                     sclk_mhz_min=round(min(c)), boost_mhz=2400, samples=len(w), source="amdgpu hwmon power1_input / freq1_input, 0.25 s period, timed region only")
 
 
+DUMP_SAMPLE = 1 << 21           # elements kept of a larger output (8 MB as float32); at most two such arrays per config: well under 64 MB in all
+
+
+def _sample(pieces, n=DUMP_SAMPLE, seed=0):
+    """float32 numpy: the concatenation of the flattened tensors `pieces`, or, when it holds more than `n` elements, the `n` elements at
+    fixed seeded positions (sorted, the same positions for the same total size)"""
+    pieces = [p.reshape(-1) for p in pieces]
+    total = sum(p.numel() for p in pieces)
+    if total <= n:
+        return torch.cat([p.float() for p in pieces]).cpu().numpy() if pieces else np.zeros(0, np.float32)
+    idx = np.sort(np.random.default_rng(seed).integers(0, total, n))
+    out, off = [], 0
+    for p in pieces:
+        lo, hi = np.searchsorted(idx, [off, off + p.numel()])
+        if hi > lo:
+            out.append(p[torch.from_numpy(idx[lo:hi] - off).to(p.device)].float().cpu())
+        off += p.numel()
+    return torch.cat(out).numpy()
+
+
+def _ids(x):
+    """float64 numpy of token ids / frame numbers / counts (a tensor, a number or a nested list of them)"""
+    if torch.is_tensor(x):
+        return x.detach().cpu().to(torch.float64).numpy().reshape(-1)
+    if isinstance(x, (list, tuple)):
+        return np.concatenate([_ids(v) for v in x]) if len(x) else np.zeros(0, np.float64)
+    return np.asarray([x], np.float64)
+
+
+def _frame_rows(wanted):
+    """sharded.ShardedMemory.frames_of lists, [(kind, segment or node, row)] per retrieved row -> float64 [n, 3] (kind 0 = a frame of the
+    feature bank, 1 = a centroid row of a merged node)"""
+    rows = [(0.0 if kind == "frame" else 1.0, i, f) for w in wanted for (kind, i, f) in w]
+    return np.asarray(rows, np.float64).reshape(-1, 3)
+
+
+def collect_outputs(pipe, config, sharded):
+    """What the last timed step handed its caller (pipe.last), as {name: float32 / float64 array}: token ids, context length, retrieved frame
+    numbers, a crc32 per retrieved path text, and seeded samples of the encoded features and of the image embeddings the answer prefill read."""
+    import zlib
+    last, out = pipe.last, {}
+    if config == "C5":
+        rounds = last["rounds"]
+        out["round_retrieved_frames"] = _frame_rows([w for r in rounds for w in r["wanted"]])
+        out["round_path_text_crc32"] = _ids([[zlib.crc32(t.encode()) for t in r["path_text"]] for r in rounds if r["path_text"] is not None])
+        if any("context" in r for r in rounds):
+            out["round_context_tokens"] = _ids([r.get("context", -1) for r in rounds])
+        if any(r.get("tokens") is not None for r in rounds):
+            out["round_tokens"] = _ids([r["tokens"] for r in rounds if r.get("tokens") is not None])
+        out["encode_features"] = _sample([pipe.round_feats[-1]])
+        return out
+    out["encode_features"] = _sample([pipe.feats])
+    if config == "C1":
+        out["kmeans_labels"] = _ids(last["labels"])
+        out["kmeans_reduced"] = _sample([last["reduced"]], seed=1)
+        return out
+    if last.get("path_text") is not None:
+        out["path_text_crc32"] = _ids([zlib.crc32(t.encode()) for t in last["path_text"]])
+    if sharded:
+        out["retrieved_frames"] = _frame_rows(last["wanted"])
+        if last.get("image_embeddings") is not None:
+            out["answer_image_embeddings"] = _sample([last["image_embeddings"]], seed=1)
+    else:
+        short_emb = U.cat_frames(last["short"]).view(-1, last["short"][0].shape[-1])
+        out["answer_image_embeddings"] = _sample([short_emb] + [t.reshape(-1, t.shape[-1]) for t in last["path_feats"]], seed=1)
+    if last.get("first_token") is not None:
+        out["first_token"] = _ids(last["first_token"])
+        out["context_tokens"] = _ids(last["context"])
+    return out
+
+
+def dump_outputs(arrays, d):
+    os.makedirs(d, exist_ok=True)
+    assert sum(v.nbytes for v in arrays.values()) <= 64 << 20, {k: v.nbytes for k, v in arrays.items()}
+    for k, v in arrays.items():
+        assert v.dtype in (np.float32, np.float64), (k, v.dtype)
+        np.save(os.path.join(d, k + ".npy"), v)
+    return {k: list(v.shape) for k, v in sorted(arrays.items())}
+
+
 def relaunch_one_rank_per_gpu(n):
     """`python bench.py --gpus N` typed as a bare command (no torch.distributed.run around it): start the N ranks ourselves, exactly as
     the task brief's launcher would (one process per GPU, rendezvous on 127.0.0.1, a free port), pass the arguments through and hand
@@ -686,6 +772,9 @@ def main():
         dt = time.perf_counter() - t0
         prof = kt.summary()
         km_infos = [i.cpu().tolist() for i in kt.aux.get("kmeans_info", [])]
+    dumped = None
+    if a.dump_outputs and rank == 0:          # before the side measurements below, which run more steps on the same pipeline
+        dumped = dump_outputs(collect_outputs(pipe, config, sharded), a.dump_outputs)
     t_enc = sum(e0.elapsed_time(e1) for e0, e1 in pipe.enc_events) / 1e3
     if world > 1:
         import torch.distributed as dist
@@ -815,6 +904,8 @@ def main():
                            weights="random-init", launcher="self (bare command)" if os.environ.get("SC_BENCH_SELF_LAUNCHED") == "1" else
                            ("torch.distributed.run" if world > 1 else "single process")),
                roofline=roof, roofline_stages=stages, stages=per, power=power.summary(), build=ops.build_info())
+    if dumped is not None:
+        out["dumped_outputs"] = dict(dir=a.dump_outputs, shapes=dumped)
     # rounds are compared on boxes whose chips hold 1.74 - 1.93 GHz under the same 1400 W cap (+-4 % on `value`): the MFMA-bound share of the
     # step (GEMM + attention launches of the encode and the prefill) rescaled to a 1900 MHz shader clock, the rest left as measured
     pw = out.get("power") or {}

@@ -25,7 +25,8 @@ def build(force: bool = False, jobs: int = 0) -> str:
     if force:
         subprocess.check_call(["make", "-s", "-C", CSRC, "clean"])
     if force or needs_build():
-        j = jobs or (os.cpu_count() or 4)
+        # MAX_JOBS when set, else the CPUs this process may run on; at most 16 (os.cpu_count() counts the whole machine's)
+        j = jobs or min(16, int(os.environ.get("MAX_JOBS") or 0) or len(os.sched_getaffinity(0)))
         subprocess.check_call(["make", "-s", f"-j{j}", "-C", CSRC])
     return LIB
 

@@ -121,13 +121,13 @@ def test_a_rank_that_never_arrives_raises_on_the_others_within_the_timeout():
 
 
 def test_bench_preflight_reports_one_json_error_line_without_a_gpu():
-    """`bench.py --preflight` on a box where the check fails (no GPU here): ONE JSON line, exit code 3 - what a launcher script can act on."""
+    """`bench.py --preflight` where the check fails (no GPU visible): ONE JSON line, exit code 3 - what a launcher script can act on.  On a
+    box with GPUs the child is started with every device hidden, so the failing leg runs there too; the passing legs are in
+    test_gpu_sharded.py."""
     import json, subprocess, sys
-    if torch.cuda.is_available():
-        import pytest
-        pytest.skip("the failing leg needs a box without a GPU; the passing legs are in test_gpu_sharded.py")
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--preflight"], capture_output=True, text=True, timeout=300)
+    env = dict(os.environ, HIP_VISIBLE_DEVICES="-1", CUDA_VISIBLE_DEVICES="-1")
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--preflight"], env=env, capture_output=True, text=True, timeout=300)
     assert r.returncode == 3
     rec = json.loads(r.stdout.strip().splitlines()[-1])
     assert rec["preflight"] == "error" and "GPU" in rec["error"]

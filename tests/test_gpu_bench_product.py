@@ -38,3 +38,32 @@ def test_product_step_with_the_llm_as_chunk_captioner():
     again = pipe.step()
     assert pipe.last["context"] == ctx_plain and int(pipe.last["first_token"][0, 0]) == tok_plain
     assert [n.text for n in again["tree"]] == [n.text for n in plain["tree"]]
+
+
+def test_bench_dump_outputs_writes_what_the_last_timed_step_computed(tmp_path):
+    """`bench.py --steps 2 --dump-outputs DIR` (C2 on a 440-frame stream): the record counts the 2 timed steps and their ms_per_step, and DIR holds
+    float .npy files of at most 64 MB in all - the encoded-feature sample equals the same seeded sample of a fresh step's features in this
+    process (same inputs, same kernels), the retrieved path's crc32s those of that step."""
+    import json
+    import subprocess
+    import zlib
+    import numpy as np
+    import bench
+    d = str(tmp_path / "dump")
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--config", "C2", "--frames", "440", "--steps", "2", "--warmup", "0",
+                        "--no-cpu-baseline", "--dump-outputs", d], cwd=ROOT, capture_output=True, text=True, timeout=600)
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert r.returncode == 0 and len(lines) == 1, r.stdout[-2000:] + r.stderr[-4000:]
+    rec = json.loads(lines[0])
+    assert rec["steps"] == 2 and rec["ms_per_step"] > 0 and rec["dumped_outputs"]["dir"] == d
+    names = sorted(f[:-4] for f in os.listdir(d))
+    assert names == sorted(rec["dumped_outputs"]["shapes"]) == ["answer_image_embeddings", "encode_features", "path_text_crc32"]
+    got = {k: np.load(os.path.join(d, k + ".npy")) for k in names}
+    assert all(v.dtype in (np.float32, np.float64) for v in got.values()) and sum(v.nbytes for v in got.values()) <= 64 << 20
+    assert got["encode_features"].shape == (bench.DUMP_SAMPLE,) and np.isfinite(got["encode_features"]).all()
+    pipe = bench.Pipeline(torch.device("cuda:0"), 440, with_llm=False)
+    pipe.step()
+    mine = bench.collect_outputs(pipe, "C2", False)
+    np.testing.assert_allclose(got["encode_features"], mine["encode_features"], rtol=1e-3, atol=1e-3)
+    assert got["path_text_crc32"].tolist() == [zlib.crc32(t.encode()) for t in pipe.last["path_text"]] == mine["path_text_crc32"].tolist()
+    np.testing.assert_allclose(got["answer_image_embeddings"], mine["answer_image_embeddings"], rtol=1e-3, atol=1e-3)

@@ -1,6 +1,6 @@
 """GPU: the sharded (N > 1) code path of bench.py run at world size 1 (`--force-sharded`) must equal the single-GPU step through the
 reference-seam functions on the same stream — same tree, same retrieved frames, bit-identical [short | long] feature block
-(VERDICT r01 item 1).  The multi-rank control flow itself is covered on CPU by tests/test_sharded_gloo.py (gloo, world 2, 3, 4 and 8); the full-size C4 / C5 jobs run here as 8 processes on the one GPU."""
+(VERDICT r01 item 1).  The multi-rank control flow itself is covered on CPU by tests/test_sharded_gloo.py (gloo, world 2, 3, 4 and 8); the full-size C4 / C5 jobs run as 8 processes, one per GPU, where a box has 8 GPUs."""
 import os
 import sys
 
@@ -232,6 +232,9 @@ def test_dp_lloyd_processes_retrieve_and_prefill_like_one(nproc):
 
 
 _full_size_one = {}          # tag -> the 1-process record of a full-size job (shared by the tests that compare against it)
+# the 8-rank jobs run one rank per GPU: the 2-4 rank jobs above share device 0, eight ranks on one device are not started
+EIGHT_GPUS = pytest.mark.skipif(torch.cuda.device_count() < 8, reason=f"needs 8 GPUs, found {torch.cuda.device_count()}")
+EIGHT_RANKS_ENV = {"SC_DIST_BACKEND": "gloo"}
 
 
 def _one_process_record(tag, cfg_args):
@@ -241,11 +244,11 @@ def _one_process_record(tag, cfg_args):
 
 
 def _full_size_pair(cfg_args, tag):
-    """the SAME full-size job as ONE process and as EIGHT processes (bare command: bench.py starts its ranks; all on device 0, gloo with host
+    """the SAME full-size job as ONE process and as EIGHT processes (bare command: bench.py starts its ranks; one rank per GPU, gloo with host
     staging); both JSON lines are left under gpurun_out/ when that directory exists (copied to profiles/ by hand)"""
     import json
     one = _one_process_record(tag, cfg_args)
-    eight = _bench_json(cfg_args + ["--gpus", "8"], {"SC_ALL_RANKS_ON_GPU0": "1", "SC_DIST_BACKEND": "gloo"}, nproc=8, launcher="bare", timeout=1100)
+    eight = _bench_json(cfg_args + ["--gpus", "8"], EIGHT_RANKS_ENV, nproc=8, launcher="bare", timeout=1100)
     out = os.path.join(ROOT, "gpurun_out")
     if os.path.isdir(out):
         with open(os.path.join(out, f"r04_{tag}_1proc_vs_8proc_one_gpu.jsonl"), "w") as f:
@@ -254,13 +257,14 @@ def _full_size_pair(cfg_args, tag):
     return one, eight
 
 
+@EIGHT_GPUS
 @pytest.mark.timeout(1500)
 def test_c4_full_size_4096_frames_in_8_processes_equals_one_process():
     """BASELINE.json configs[3] AT ITS SIZE: ONE 4096-frame stream = 103 chunks dealt to EIGHT ranks by whole chunks
     (12-13 chunks = 480-520 frames each), rank-local encode + captions, the single-stream tree policy (ten merges' worth of depth-0 nodes,
     ONE merge k-means T = 400 on the rank owning the group), Ref broadcast, all-gather of the selected rows, 49 k-token 7B prefill on rank 0.
-    Eight processes share this box's one GPU; the collectives are gloo with host staging (RCCL refuses two ranks per device, so RCCL's own
-    transport stays unmeasured).  Retrieved frames + path text, context length and the first generated token equal the 1-process run."""
+    Eight processes, one per GPU; the collectives are gloo with host staging (the same transport as the 2-4 process jobs above, which share
+    one device; RCCL's own transport is test_two_ranks_on_two_gpus_over_rccl_equal_one_process).  Retrieved frames + path text, context length and the first generated token equal the 1-process run."""
     args = ["--config", "C4", "--steps", "1", "--warmup", "0", "--no-cpu-baseline", "--decode-tokens", "0"]
     one, eight = _full_size_pair(args, "c4_4096")
     assert eight["config"]["frames_total"] == 4096 and "4096-frame" in eight["metric"]
@@ -269,6 +273,7 @@ def test_c4_full_size_4096_frames_in_8_processes_equals_one_process():
     assert eight["config"]["frames_rank0"] in (480, 520)
 
 
+@EIGHT_GPUS
 @pytest.mark.timeout(1500)
 def test_c4_full_size_in_8_processes_with_the_data_parallel_lloyd_equals_one_process():
     """The same full-size C4 job with `--dp-lloyd`: the T = 400 x D = 2 064 384 merge k-means runs on EIGHT ranks at once, each on the columns of
@@ -277,7 +282,7 @@ def test_c4_full_size_in_8_processes_with_the_data_parallel_lloyd_equals_one_pro
     token as ONE process, because the fit is bit-identical by construction of the reduction spec."""
     args = ["--config", "C4", "--steps", "1", "--warmup", "0", "--no-cpu-baseline", "--decode-tokens", "0"]
     one = _one_process_record("c4_4096", args)
-    eight = _bench_json(args + ["--gpus", "8", "--dp-lloyd"], {"SC_ALL_RANKS_ON_GPU0": "1", "SC_DIST_BACKEND": "gloo"}, nproc=8, launcher="bare", timeout=1100)
+    eight = _bench_json(args + ["--gpus", "8", "--dp-lloyd"], EIGHT_RANKS_ENV, nproc=8, launcher="bare", timeout=1100)
     assert eight["n_gpus"] == 8 and eight["config"]["frames_total"] == 4096
     for k in ("retrieval_crc32", "first_token", "context_tokens"):
         assert one["config"][k] == eight["config"][k], (k, one["config"][k], eight["config"][k])
@@ -285,6 +290,40 @@ def test_c4_full_size_in_8_processes_with_the_data_parallel_lloyd_equals_one_pro
     assert dp["fits_last_step"] == 1 and dp["bytes_moved_last_step"] > 400 * 576 * 3584 * 2 * 7 // 8
 
 
+@pytest.mark.timeout(1500)
+@pytest.mark.parametrize("dp_lloyd", [False, True])
+def test_c4_full_size_4096_frames_in_4_processes_equals_one_process(dp_lloyd):
+    """The full-size C4 job of the two 8-rank tests above on a box with fewer GPUs: FOUR processes sharing device 0 (torch.distributed.run,
+    gloo with host staging), 25-26 chunks = 1000-1040 frames per rank; with `--dp-lloyd` the T = 400 merge k-means runs on the columns of
+    the four ranks.  Retrieved frames + path text, context length and the first generated token equal the 1-process run."""
+    args = ["--config", "C4", "--steps", "1", "--warmup", "0", "--no-cpu-baseline", "--decode-tokens", "0"]
+    one = _one_process_record("c4_4096", args)
+    four = _bench_json(args + ["--gpus", "4"] + (["--dp-lloyd"] if dp_lloyd else []), {"SC_ALL_RANKS_ON_GPU0": "1", "SC_DIST_BACKEND": "gloo"},
+                       nproc=4, launcher="torchrun", timeout=1100)
+    assert four["n_gpus"] == 4 and four["config"]["frames_total"] == 4096 and four["config"]["frames_rank0"] == 1000
+    for k in ("retrieval_crc32", "first_token", "context_tokens"):
+        assert one["config"][k] == four["config"][k], (k, one["config"][k], four["config"][k])
+    if dp_lloyd:
+        dp = four["collective"]["dp_lloyd"]
+        assert dp["fits_last_step"] == 1 and dp["bytes_moved_last_step"] > 400 * 576 * 3584 * 2 * 3 // 4
+
+
+@pytest.mark.timeout(1500)
+def test_c5_session_in_4_processes_equals_one_process():
+    """The C5 session of the 8-rank test below on a box with fewer GPUs, at a smaller size: 2 rounds of 440 frames (11 chunks each, one merge
+    per round) over FOUR processes sharing device 0 (torch.distributed.run, gloo with host staging), the ONE memory tree persisting across
+    the rounds.  Per round: retrieved frames + path text, context length and the 64 decoded tokens equal the 1-process session."""
+    args = ["--config", "C5", "--rounds", "2", "--frames", "440", "--steps", "1", "--warmup", "0", "--no-cpu-baseline"]
+    one = _bench_json(args + ["--force-sharded"], {})
+    four = _bench_json(args + ["--gpus", "4"], {"SC_ALL_RANKS_ON_GPU0": "1", "SC_DIST_BACKEND": "gloo"}, nproc=4, launcher="torchrun")
+    assert four["n_gpus"] == 4 and four["config"]["frames_total"] == 880 and len(four["config"]["rounds"]) == 2
+    for r, (a, b) in enumerate(zip(one["config"]["rounds"], four["config"]["rounds"])):
+        assert a == b, (r, a, b)
+        assert a["tokens_crc32"] is not None and a["context"] > 5 * 576 + 23040
+    assert one["config"]["context_tokens"] == four["config"]["context_tokens"]
+
+
+@EIGHT_GPUS
 @pytest.mark.timeout(2400)
 def test_c5_full_size_8192_frames_8_rounds_in_8_processes_equals_one_process():
     """BASELINE.json configs[4] AT ITS SIZE: ONE 8192-frame ego stream in 8 question rounds of 1024 new frames, every round sharded over

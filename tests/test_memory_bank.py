@@ -3,6 +3,7 @@ JsonMemoryLoader / patched FAISS search / search_memory (tools/make_golden.py ge
 top-k is provided by the oracle here (no GPU); tests/test_gpu_memory.py runs the same cases through sc_sim_topk."""
 import json
 import os
+import time
 import types
 import zlib
 
@@ -88,10 +89,14 @@ def test_build_prompt_with_search_memory_only_related():
     assert U.build_prompt_with_search_memory_only_related("q?", "User", None, fake, meta, "[|User|]", "[|AI|]", "AI") is None
 
 
-def test_dialogue_index_is_persisted_append_only(tmp_path):
+def test_dialogue_index_is_persisted_append_only(tmp_path, monkeypatch):
     """Round 6 (reference local_doc_qa.py:242-251 re-opens the saved index and adds to it): after every question only the
     NEW documents and the NEW vectors are written - index.jsonl grows by lines, index.npy by rows behind a fixed-size header - and a fresh
     process reads the same index back; a history that is not an extension of what is on disk rewrites the files."""
+    # save_local_memory files each turn under today's date, and the date is part of the document text that FakeEmb hashes into a vector:
+    # the "umbrella" nearest-neighbour check below holds only for a fixed date, so the test pins one instead of reading the clock
+    day = time.strptime("2026-09-29", "%Y-%m-%d")
+    monkeypatch.setattr(MU, "time", types.SimpleNamespace(strftime=time.strftime, localtime=lambda *a: day))
     args = types.SimpleNamespace(memory_basic_dir=str(tmp_path), memory_file="memory_0.json", language="en")
     lm = Q.LocalMemoryRetrieval()
     lm.init_cfg("minilm-l6", top_k=1, language="en", embedder=FakeEmb())
