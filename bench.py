@@ -1,8 +1,12 @@
 #!/usr/bin/env python3
 """bench.py — headline benchmark of the streaming hot path on MI355X (driver contract in the task brief).
 
-  python bench.py --gpus N --steps K --warmup W [--config C1|C2|C3|C4|C5] [--dump-outputs DIR]
+  python bench.py --gpus N --steps K --warmup W [--config C1|C2|C3|C4|C5] [--dump-outputs DIR] [--full]
   (N > 1: one rank per GPU under torch.distributed.run, as the driver launches it; typed as a bare command it starts the N ranks itself)
+
+A plain run sets up, warms up, times the K steps, writes --dump-outputs and prints the line: every figure in it comes from the timed steps.
+--full adds the measurements that take runs of their own: the CPU baseline (C2 / C3), the k-means forced through 10 Lloyd passes, decode
+tokens/s, the `session` and `product` legs (C3, N = 1) and, for N > 1, rank 0's encode alone inside the same job.
 
 A "step" is one pass of the hot path over one synthetic 336x336 frame stream:
   encode   uint8 frames -> fused preprocess/patchify -> ViT-L/14-336 (23 layers) -> mlp2x_gelu projector   [MFMA]
@@ -52,10 +56,13 @@ def parse():
     ap.add_argument("--config", choices=["C1", "C2", "C3", "C4", "C5"], default=None)
     ap.add_argument("--rounds", type=int, default=8, help="C5: question rounds per session (1024 new frames each)")
     ap.add_argument("--frames", type=int, default=None, help="frames per GPU (C2/C3) or in total (C1/C4); default: the config's size")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline measurement, also run the side measurements that take runs of their own (CPU baseline, 10-pass k-means, "
+                         "decode tokens/s, session, product; N > 1: the 1-GPU encode rate of the same job); off: the line holds what the timed steps measured")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: leave the CPU baseline out")
     ap.add_argument("--no-llm", action="store_true", help="C2 workload: stop after retrieval (no 7B prefill)")
-    ap.add_argument("--decode-tokens", type=int, default=512, help="decode tokens measured AFTER the timed region (reported separately)")
-    ap.add_argument("--cpu-frames", type=int, default=64, help="frames of the CPU-baseline slice (SURVEY 8(d): 64 = C1's encode)")
+    ap.add_argument("--decode-tokens", type=int, default=512, help="--full: decode tokens measured AFTER the timed region (reported separately)")
+    ap.add_argument("--cpu-frames", type=int, default=64, help="--full: frames of the CPU-baseline slice (SURVEY 8(d): 64 = C1's encode)")
     ap.add_argument("--force-sharded", action="store_true", help="exercise the N>1 code path with world size 1 (testing)")
     ap.add_argument("--dp-lloyd", action="store_true", help="N > 1: the merge group's k-means data-parallel over columns (sharded._dp_lloyd; "
                     "same bits as the owner-rank path, which stays the default until a multi-GPU box has run it); = SC_DP_LLOYD=1")
@@ -63,11 +70,11 @@ def parse():
                     help="check the job instead of running it: visible GPUs, chunk partition, free HBM per rank, one 1-element all-gather and one "
                          "point-to-point round per peer; ONE JSON line, exit code 0 / 3")
     ap.add_argument("--session", type=int, default=4, metavar="SEGMENTS",
-                    help="AFTER the headline measurement (C3, one GPU): a stream of SEGMENTS segments with a --decode-tokens answer each, serial vs "
+                    help="--full, AFTER the headline measurement (C3, one GPU): a stream of SEGMENTS segments with a --decode-tokens answer each, serial vs "
                          "reader/updater || QA-decode overlapped on two CU partitions (streamchat_amd/session.py); reported as `session`; 0 = off")
     ap.add_argument("--session-decode-cus", type=int, nargs="*", default=[128], help="CUs of the decode partition(s) to try in --session (multiples of 32)")
     ap.add_argument("--with-captions", type=int, nargs="?", const=2, default=1, metavar="STEPS",
-                    help="AFTER the headline measurement: STEPS more steps (default 1; 0 = off) in which the chunk captioner is the HIP 7B model itself "
+                    help="--full, AFTER the headline measurement: STEPS more steps (default 1; 0 = off) in which the chunk captioner is the HIP 7B model itself "
                          "(one 23 k-token prefill + 128 new tokens per 40-frame chunk through llm.BatchDecoder, reference utiles.py:539-559), "
                          "reported as a separate `product` object; `value` is untouched (the metric names encode+select+retrieve+prefill)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
@@ -720,7 +727,7 @@ def main():
     ctx = DD.DistContext(rank, world, dev, os.environ.get("SC_DIST_BACKEND", "nccl") if world > 1 else "nccl")
     dist_warm = DD.warm_up(ctx)                               # every communicator (collective + one point-to-point pair per peer) exists before step 1
     config = a.config or ("C2" if a.no_llm else "C3")
-    full = config in ("C3", "C4", "C5") and not a.no_llm
+    with_llm = config in ("C3", "C4", "C5") and not a.no_llm
     if config == "C1":
         n_total, scaling = a.frames or 64, "strong"
     elif config == "C5":
@@ -734,11 +741,11 @@ def main():
         sys.exit("C1 (64 frames, one k-means over all of them) is a single-GPU configuration")
     if config == "C5":
         # every top-level merged node adds one retrieved chunk (23 040 tokens) to the context (utiles.py:715-748): ~210 k tokens by round 8
-        pipe = Pipeline(dev, 0, with_llm=full and rank == 0, ctx=ctx, max_seq=(a.rounds + 2) * 23040 + 8192)
+        pipe = Pipeline(dev, 0, with_llm=with_llm and rank == 0, ctx=ctx, max_seq=(a.rounds + 2) * 23040 + 8192)
         pipe.prepare_rounds(a.rounds, n_total // a.rounds)
         run_step = pipe.session
     else:
-        pipe = Pipeline(dev, n_total, with_llm=full and rank == 0, ctx=ctx, kmeans_k=8 if config == "C1" else None)
+        pipe = Pipeline(dev, n_total, with_llm=with_llm and rank == 0, ctx=ctx, kmeans_k=8 if config == "C1" else None)
         run_step = pipe.step_sharded if sharded else pipe.step
 
     def barrier():
@@ -750,10 +757,10 @@ def main():
     for _ in range(a.warmup):
         run_step()
     barrier()
-    # the 1-GPU encode rate inside the same job (N > 1 only): rank 0 encodes its shard alone while the other ranks wait at the barrier,
+    # the 1-GPU encode rate inside the same job (N > 1, --full): rank 0 encodes its shard alone while the other ranks wait at the barrier,
     # so that 1 -> N encode scaling (north_star: ">= 6x frame-encode scaling at 8 GPUs") can be read off ONE record
     enc_solo = None
-    if world > 1:
+    if world > 1 and a.full:
         solo_frames = pipe.round_frames[0] if config == "C5" else pipe.frames
         if rank == 0 and solo_frames.shape[0]:
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -818,7 +825,7 @@ def main():
     # bytes: one read of X per Lloyd iteration; 2x = what the two-pass kernel moves), decode below
     stages = dict(vit_gemm=mfma_roof("k_gemm* (ViT-L + projector)", fam("k_gemm", ("encode",))),
                   vit_attention=mfma_roof("k_attn<64> S=577", fam("k_attn", ("encode",))))
-    if full:
+    if with_llm:
         stages.update(llm_gemm=mfma_roof("k_gemm* (Qwen2-7B prefill)", fam("k_gemm", ("prefill",))),
                       llm_attention=mfma_roof("k_attn<128> causal GQA", fam("k_attn", ("prefill",))))
     kn, kms, kw = fam("kmeans_fit")
@@ -829,7 +836,7 @@ def main():
                                 achieved=round(gbs, 1), peak=HBM_PEAK_GBS, unit="GB/s", frac=round(gbs / HBM_PEAK_GBS, 4),
                                 reads_of_X_per_lloyd_iteration=round((iters / kn + 1) / (iters / kn), 3),      # n + 1 reads for n iterations (rounds 1-5: 2 n)
                                 frac_counting_every_read_of_X=round((iters / kn + 1) / (iters / kn) * gbs / HBM_PEAK_GBS, 4))
-    if kn and world == 1 and pipe.feats.shape[0] >= 400:
+    if a.full and kn and world == 1 and pipe.feats.shape[0] >= 400:
         # the same merge k-means (T = 400, K = 5, D = 2 064 384, the step's own features) forced through all 10 Lloyd iterations (tol < 0): a
         # fixed amount of work whatever the stream does.  (The synthetic stream cuts its scenes at the chunk size, so the timed step's own run
         # converges after two passes.  Moving the cuts - tried in round 6 with 37-frame scenes - changes what the question retrieves: 39 778
@@ -859,13 +866,13 @@ def main():
                     "memory tree (one merge k-means per round), BERT-large-CLS tree search + MiniLM dialogue memory, LongVA-7B prefill + 64-token decode on rank 0")
     per_gpu = n_total // world
     if config == "C5":
-        metric = (f"frames/sec over a multi-round session (per round: encode+select+retrieve{'+7B prefill+64-token decode' if full else ''}), "
+        metric = (f"frames/sec over a multi-round session (per round: encode+select+retrieve{'+7B prefill+64-token decode' if with_llm else ''}), "
                   f"{n_total}-frame ego stream" + (f" sharded over {world} GPUs" if world > 1 else ""))
-    elif config == "C4" and full:
+    elif config == "C4" and with_llm:
         metric = f"frames/sec end-to-end (encode+select+retrieve+7B prefill), {n_total}-frame stream sharded over the ranks"
-    elif full and world == 1:
+    elif with_llm and world == 1:
         metric = "frames/sec end-to-end (encode+select+retrieve+7B prefill), 1024-frame stream"           # BASELINE.json's metric, verbatim
-    elif full:          # the same workload per GPU; the line says how many frames the job processed in total
+    elif with_llm:      # the same workload per GPU; the line says how many frames the job processed in total
         metric = (f"frames/sec end-to-end (encode+select+retrieve+7B prefill), {n_total}-frame stream in total = {per_gpu} frames per GPU x "
                   f"{world} GPUs (ONE stream sharded by whole chunks)")
     else:
@@ -877,8 +884,9 @@ def main():
                # frame-encode throughput of the whole job (max over ranks of the HIP-event time around each rank's encode stage): the
                # figure the ">= 6x frame-encode scaling at 8 GPUs" target is about; `value` additionally contains the stages below
                encode_frames_per_s=round(enc_fps, 1), encode_ms_per_step=round(t_enc / a.steps * 1e3, 2))
-    if world > 1:
+    if world > 1 and a.full:
         out["encode_frames_per_s_1gpu_same_job"] = None if enc_solo is None else round(enc_solo, 1)
+    if world > 1:
         out["scaling_note"] = (
             f"encode (ViT-L + projector) and chunk captions are rank-local: {n_total} frames over {world} GPUs, no data-path collective; "
             "select / retrieve run on the whole stream from metadata identical on every rank (one merge k-means on the rank owning the "
@@ -886,8 +894,8 @@ def main():
             "their final position: only rank 0 allocates, only the rows it lacks move - `collective`); the 7B prefill"
             + (" + decode" if config == "C5" else "") + " is SERIAL on rank 0 (single-GPU, no TP) and its context (~49 k tokens) does not "
             "grow with the stream, so `value` scales with the frames per step while ms_per_step stays that of the serial tail + one "
-            "rank's encode; read encode scaling from encode_frames_per_s against encode_frames_per_s_1gpu_same_job (rank 0 encoding its "
-            "shard alone, other ranks idle at a barrier) or against the N = 1 record")
+            "rank's encode; read encode scaling from encode_frames_per_s against encode_frames_per_s_1gpu_same_job (--full: rank 0 encoding "
+            "its shard alone, other ranks idle at a barrier) or against the N = 1 record")
     if world > 1:
         out["dist_warm_up"] = dict(dist_warm, timeout_s=float(os.environ.get("SC_DIST_TIMEOUT_S", DD.DEFAULT_TIMEOUT_S)),
                                    note="communicators (one all-gather, one point-to-point round per peer) created before the warm-up steps")
@@ -926,7 +934,7 @@ def main():
                                         retrieval_crc32=zlib.crc32(json.dumps(dict(path_text=list(r["path_text"]), wanted=r["wanted"])).encode()),
                                         tokens_crc32=None if r.get("tokens") is None else zlib.crc32(json.dumps([int(t) for t in r["tokens"]]).encode()))
                                    for r in pipe.last["rounds"]]
-    if full and a.decode_tokens > 0 and world == 1 and config != "C5":
+    if a.full and with_llm and a.decode_tokens > 0 and world == 1 and config != "C5":
         rate = pipe.decode_rate(a.decode_tokens)         # greedy, batch 1, after the timed region (512 tokens)
         ctxlen = pipe.last["context"] + a.decode_tokens / 2
         gb_tok = 14.1 + 2 * 28 * 4 * 128 * ctxlen * 2 / 1e9       # fp16 weights incl. lm_head + KV bytes per token
@@ -944,9 +952,9 @@ def main():
         except Exception:
             pass
     # (the contract's cpu_baseline before the optional side measurements: whatever happens in them, the line carries it)
-    if not a.no_cpu_baseline and world == 1 and config in ("C2", "C3"):
+    if a.full and not a.no_cpu_baseline and world == 1 and config in ("C2", "C3"):
         out["cpu_baseline"] = cpu_baseline(pipe, a.cpu_frames, max((i[0] + 1 for i in km_infos[-1:]), default=3))
-    if a.session > 0 and full and world == 1 and config == "C3" and a.decode_tokens > 0:
+    if a.full and a.session > 0 and with_llm and world == 1 and config == "C3" and a.decode_tokens > 0:
         # a side measurement must never take the headline line with it: an exception is recorded, and a run that does not come back (two host
         # threads, two streams) is cut by a watchdog that prints the line as it stands and ends the process
         import threading
@@ -965,7 +973,7 @@ def main():
         finally:
             dog.cancel()
             torch.cuda.empty_cache()
-    if a.with_captions and full and world == 1 and config == "C3":
+    if a.full and a.with_captions and with_llm and world == 1 and config == "C3":
         # what the metric leaves out (SURVEY 8(f).1 "the true wall-clock dominator"), measured once on this code: the same step with the HIP
         # 7B model as the chunk captioner.  Separate object; `value` above is the headline metric and does not contain it.
         try:

@@ -1,4 +1,4 @@
-"""GPU: the `product` leg of bench.py (round 4; on by default in the driver's bench line): the C3 step with the HIP LLM itself as chunk captioner
+"""GPU: the `product` leg of `bench.py --full` (round 4): the C3 step with the HIP LLM itself as chunk captioner
 + merge summariser (reference utiles.py:539-559,591-607) through llm.BatchDecoder.  A 2-layer model at the Qwen2-7B widths keeps it short; what
 is checked is the plumbing the driver line depends on: every chunk of the update goes through ONE batched generate, the record is complete and
 self-consistent, the step's retrieval still works on the generated captions, and the headline path is untouched afterwards."""
@@ -67,3 +67,24 @@ def test_bench_dump_outputs_writes_what_the_last_timed_step_computed(tmp_path):
     np.testing.assert_allclose(got["encode_features"], mine["encode_features"], rtol=1e-3, atol=1e-3)
     assert got["path_text_crc32"].tolist() == [zlib.crc32(t.encode()) for t in pipe.last["path_text"]] == mine["path_text_crc32"].tolist()
     np.testing.assert_allclose(got["answer_image_embeddings"], mine["answer_image_embeddings"], rtol=1e-3, atol=1e-3)
+
+
+def test_plain_bench_runs_no_side_measurement_and_full_adds_them():
+    """A plain `bench.py` run prints what its timed steps measured and nothing else; `--full` adds the side measurements that take runs of their
+    own.  C2 on a 440-frame stream (one merge k-means T = 400): plain, no CPU baseline and no forced 10-pass k-means; with `--full` (CPU baseline
+    left out to keep it short) the k-means is forced through its 10 Lloyd passes, and the headline fields say the same things."""
+    import json
+    import subprocess
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--config", "C2", "--frames", "440", "--steps", "1", "--warmup", "0"]
+    recs = []
+    for extra in ([], ["--full", "--no-cpu-baseline"]):
+        r = subprocess.run(cmd + extra, cwd=ROOT, capture_output=True, text=True, timeout=600)
+        lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+        assert r.returncode == 0 and len(lines) == 1, r.stdout[-2000:] + r.stderr[-4000:]
+        recs.append(json.loads(lines[0]))
+    plain, full = recs
+    assert "cpu_baseline" not in plain and "kmeans_10_passes" not in plain["roofline_stages"] and plain["roofline_stages"]["kmeans"]["launches"] >= 1
+    assert full["roofline_stages"]["kmeans_10_passes"]["lloyd_passes"] == 10 and "cpu_baseline" not in full
+    for k in ("metric", "unit", "higher_is_better", "dtype", "steps", "warmup"):
+        assert plain[k] == full[k], k
+    assert plain["value"] > 0 and plain["ms_per_step"] > 0 and plain["config"]["retrieval_crc32"] == full["config"]["retrieval_crc32"]

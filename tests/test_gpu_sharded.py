@@ -203,7 +203,8 @@ def test_processes_retrieve_and_prefill_like_one(nproc, launcher):
     so the P2P fetch, the all-gather of the selected rows, the Ref broadcast and the caption exchange all carry data.  Retrieved frames,
     path text and the first generated token must equal the 1-process run of the same stream, and the record must say what it is."""
     one = _c4_small_one_process()
-    many = _bench_json(C4_SMALL + ["--gpus", str(nproc)], {"SC_ALL_RANKS_ON_GPU0": "1", "SC_DIST_BACKEND": "gloo"}, nproc=nproc, launcher=launcher)
+    many = _bench_json(C4_SMALL + ["--gpus", str(nproc), "--full"], {"SC_ALL_RANKS_ON_GPU0": "1", "SC_DIST_BACKEND": "gloo"}, nproc=nproc,
+                       launcher=launcher)          # --full: the record also carries rank 0's encode alone (encode_frames_per_s_1gpu_same_job)
     assert many["n_gpus"] == nproc and one["n_gpus"] == 1
     for k in ("retrieval_crc32", "first_token", "context_tokens"):
         assert one["config"][k] == many["config"][k], (k, one["config"][k], many["config"][k])

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """How much of the session's answer decode really ran BESIDE the next segment's MFMA work?  Reads a rocprofv3 kernel trace (rocpd sqlite) of
 
-    rocprofv3 --kernel-trace -d /tmp/kt -o s -- python bench.py --steps 1 --warmup 1 --no-cpu-baseline --with-captions 0 --decode-tokens 512 --session 3
+    rocprofv3 --kernel-trace -d /tmp/kt -o s -- python bench.py --full --steps 1 --warmup 1 --no-cpu-baseline --with-captions 0 --decode-tokens 512 --session 3
 
 classifies every dispatch as HBM-side (the token loop: GEMV / skinny GEMM / decode attention / merge / token selection) or MFMA-side (tile GEMMs, tile
 attention, k-means, norms of the prefill and the encoder) and measures, with a sweep over the start / end timestamps, the time during which at least one
