@@ -61,8 +61,10 @@ enum { SC_OK = 0, SC_ERR_ARG = -1, SC_ERR_WORKSPACE = -2, SC_ERR_LAUNCH = -3, SC
  *      graph == eager under sampling, no generator state on the device)
  *   8  round 6: + sc_kmeans_fit_cols (sc_kmeans_fit on a column slab of X that holds whole SC-KM2 segments, with a caller-supplied exchange of the
  *      two fp64 segment tables per iteration: the data-parallel Lloyd of a merge group, bit-identical to the 1-GPU fit at any rank count)
+ *   9  - sc_rope_f16, sc_rope_row_f16, sc_rope_qk_row_f16, sc_decode_qkv_f16 (rotary angles from `theta` with HF's fp16 roundings: superseded
+ *      since version 3 by the fp32 table of sc_rope_table_f32 and its consumers, which are what every caller uses)
  */
-#define SC_ABI_VERSION 8
+#define SC_ABI_VERSION 9
 
 int sc_abi_version(void);
 const char* sc_last_error(void);
@@ -228,23 +230,18 @@ int sc_rmsnorm_f16(const void* x, int ldx, const void* gamma, float eps, void* y
                    int cols, sc_stream_t stream);
 
 /* Qwen2 helpers.  sc_gather_rows_f16: out[r] = table[ids[r]] (embed_tokens; ids < 0 -> zero row, filled by the image
- * splice of llava_arch.py:208-343).  sc_rope_f16: rotate-half rotary embedding in place on `heads` heads of width Dh at
- * column 0 of every row (positions NULL -> pos0 + row), HF apply_rotary_pos_emb numerics. */
+ * splice of llava_arch.py:208-343). */
 int sc_gather_rows_f16(const int32_t* ids, const void* table, void* out, int rows, int H, int ldo, int vocab,
                        sc_stream_t stream);
-int sc_rope_f16(void* x, int ld, const int32_t* positions, int pos0, int rows, int heads, int Dh, float theta,
-                sc_stream_t stream);
-/* RoPE on ONE row of a [rows, ld] buffer; the row number (= token position) is read from device memory (graph-replayable). */
-int sc_rope_row_f16(void* buf, int ld, const int32_t* row_index, int heads, int Dh, float theta, sc_stream_t stream);
-/* Decode step: RoPE of the new query row q [q_heads*Dh] (position row_index[0]) and of the K part of cache row row_index[0]
- * ([rows, ld] buffer, K = the first kv_heads*Dh columns) in one launch. */
-int sc_rope_qk_row_f16(void* q, int q_heads, void* cache, int ld, const int32_t* row_index, int kv_heads, int Dh,
-                       float theta, sc_stream_t stream);
 /* Rotary embedding from fp32 projections with ONE rounding (round 3, ABI 3).  sc_rope_table_f32: tab[pos][0][j] = cos(pos * theta^(-2j/Dh))
  * * scale, tab[pos][1][j] = sin(..) * scale, j < Dh/2, pos < max_pos (fp32; scale = softmax scale * log2 e for the QUERY table, 1 for keys).
  * sc_rope_f32in_f16: x [rows, ldx] fp32 (projection + bias) -> out [rows, ldo] fp16: the first `heads` heads of width Dh rotated with the
  * table row positions[r] (or pos0 + r), `plain_cols` further columns cast unchanged (the V part of a k|v projection).
- * sc_decode_qkv_tab_f16: sc_decode_qkv_f16 with this arithmetic (tab_q scaled, tab_k not): q leaves pre-scaled for SC_ATTN_Q_PRESCALED.
+ * sc_decode_qkv_tab_f16: the fused decode-step projection block with this arithmetic (tab_q scaled, tab_k not): q leaves pre-scaled for
+ * SC_ATTN_Q_PRESCALED.  [q | k | v] = W . rmsnorm(x) + b, q and k rotated at position pos[0] (device int32), q -> q_out [q_heads*Dh], k | v ->
+ * cache row pos[0] (row stride cache_ld, K at column 0, V at kv_heads*Dh): one launch for the q / k / v projections of a decode layer (HF
+ * Qwen2Attention q_proj / k_proj / v_proj + apply_rotary_pos_emb behind reference llava_qwen.py:155).
+ *   Wq [q_heads*Dh, K], Wkv [2*kv_heads*Dh, K] (k rows then v rows), bq / bkv biases or NULL, rms_gamma [K] or NULL (no norm).
  * `tab_rows` / `rope_tab_rows` (ABI 4) = positions the table holds: a position beyond it is an error where the host knows it, clamped otherwise. */
 int sc_rope_table_f32(float* tab, int max_pos, int Dh, float theta, float scale, sc_stream_t stream);
 int sc_rope_f32in_f16(const float* x, int ldx, const float* tab, int tab_rows, const int32_t* positions, int pos0, int rows, int heads, int Dh,
@@ -303,15 +300,6 @@ int sc_attention_f16(const void* q, int ldq, const void* k, int ldk, const void*
  * 16 query rows, split-KV, non-causal = a decode step: every wave streams its own run of 32-row chunks).  Host-only query for tests and
  * profiles; the arithmetic contract of sc_attention_f16 does not depend on it. */
 int sc_attention_variant(int Dh, int Sq, int nsplit);
-
-/* Fused decode-step projection block: [q | k | v] = W . rmsnorm(x) + b, rotate-half RoPE (HF fp16 numerics) of q and k at position
- * pos[0] (device int32), q -> q_out [q_heads*Dh], k | v -> cache row pos[0] (row stride cache_ld, K at column 0, V at kv_heads*Dh).
- * One launch for the three small launches of a decode layer (q GEMV, kv GEMV, RoPE: HF Qwen2Attention q_proj / k_proj / v_proj +
- * apply_rotary_pos_emb behind reference llava_qwen.py:155); bit-identical to sc_gemv_f16 x2 + sc_rope_qk_row_f16.
- *   Wq [q_heads*Dh, K], Wkv [2*kv_heads*Dh, K] (k rows then v rows), bq / bkv biases or NULL, rms_gamma [K] or NULL (no norm). */
-int sc_decode_qkv_f16(const void* Wq, const void* Wkv, const void* bq, const void* bkv, const void* x, const void* rms_gamma,
-                      float rms_eps, void* q_out, void* cache, int cache_ld, const int32_t* pos, int q_heads, int kv_heads,
-                      int Dh, int K, float theta, sc_stream_t stream);
 
 /* ----------------------------------------------------------------------------------------------
  * Next-token selection over fp32 LM-head logits.  Replaces what HF `generate` does after the forward pass

@@ -19,7 +19,6 @@
 // steady-state loop with no mask, no row max and no O rescale (see the notes at the loop); what bounds it - LDS fragment
 // traffic and the SIMD issue port - is measured in tools/probes/ and summarised in DESIGN.md section 4.
 #include "sc_common.h"
-#include <stdlib.h>
 #include <type_traits>
 
 // attention_decode.hip (its own translation unit: default machine scheduler)
@@ -468,11 +467,6 @@ int launch_attn(const void* q, int ldq, const void* k, int ldk, const void* v, i
 
 }  // namespace
 
-static bool attn_decode_enabled() {
-    static const bool on = [] { const char* e = getenv("SC_ATTN_DECODE"); return !(e && e[0] == '0'); }();
-    return on;
-}
-
 // which machine scheduler attention.hip was built with (Makefile: iterative-ilp, or the default one if that compile failed) - sc_build_info()
 const char* sc_attn_build_tag() {
 #ifdef SC_ATTN_SCHED_FALLBACK
@@ -484,7 +478,7 @@ const char* sc_attn_build_tag() {
 
 extern "C" int sc_attention_variant(int Dh, int Sq, int nsplit) {
     if (Dh == 128 && nsplit == 1 && Sq >= 2048) return 1;
-    if (Dh == 128 && nsplit > 1 && Sq <= 16 && attn_decode_enabled()) return 3;      // (non-causal calls; a causal call of this shape runs k_attn)
+    if (Dh == 128 && nsplit > 1 && Sq <= 16) return 3;      // (non-causal calls; a causal call of this shape runs k_attn)
     return 0;
 }
 
@@ -513,7 +507,7 @@ extern "C" int sc_attention_f16(const void* q, int ldq, const void* k, int ldk, 
     SC_REQUIRE(qhs % 8 == 0 && ohs % 4 == 0, "sc_attention_f16: head strides must be multiples of 8 (q) / 4 (out)");
     const long qbs = q_batch_stride > 0 ? (long)q_batch_stride : (long)Sq * ldq, obs = o_batch_stride > 0 ? (long)o_batch_stride : (long)Sq * ldo;
     SC_REQUIRE(qbs % 8 == 0 && obs % 4 == 0, "sc_attention_f16: batch strides must be multiples of 8 (q) / 4 (out)");
-    // few query rows against a long cache with split-KV = a decode step: the per-wave streaming kernel (SC_ATTN_DECODE=0: the tile kernel)
+    // few query rows against a long cache with split-KV = a decode step: the per-wave streaming kernel
     const bool pre = (causal_flags & SC_ATTN_Q_PRESCALED) != 0;
     const float sl2_dec = pre ? 1.0f : scale * 1.4426950408889634f;
     if (sc_attention_variant(Dh, Sq, nsplit) == 3 && !causal) {

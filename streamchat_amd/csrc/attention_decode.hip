@@ -3,9 +3,6 @@
 // attention.hip is built with hipcc's iterative-ILP machine scheduler (good for the MFMA-bound tile kernel: +3 % on the 49 k prefill),
 // which costs these HBM-bound kernels 0.6-2 % (profiles/r03_run49_51_attn_sched_strategy.md): this file takes the default scheduler.
 #include "sc_common.h"
-#include <atomic>
-#include <stdlib.h>
-#include <type_traits>
 
 namespace {
 
@@ -90,7 +87,7 @@ __global__ void k_attn_combine(const float* __restrict__ part, _Float16* __restr
 //      global side: every DMA instruction fetches 4 whole rows = 8 full 128-B lines (the register path fetched 16 rows x 64 B);
 //   V: as before, swizzled rows read with ds_read_b64_tr_b16 (P.V needs V transposed);
 //   queue order per chunk c: K(c+PD) is requested as soon as the S MFMAs have read K(c)'s fragments, V(c+PD) as soon as the transpose
-//   reads of V(c) have returned, so each ring needs only DEC_PD stages: 2 x 16 KiB per wave, 128 KiB per workgroup;
+//   reads of V(c) have returned, so each ring needs only DEC_PD stages;
 //   rows past the wave's range are outside the buffer resource's extent: zeros, no memory traffic (the row part of every address
 //   stays in the VGPR offset, which is what the range check covers).
 // The MFMA operands are element for element those of the round-3 kernel: results are bit-identical to it.
@@ -115,9 +112,12 @@ __device__ unsigned long long sc_dec_trace_buf[8192 * 8];
 constexpr int DEC_NW = SC_DEC_NW, DEC_NW_LOG = DEC_NW == 8 ? 3 : (DEC_NW == 4 ? 2 : (DEC_NW == 2 ? 1 : 0));
 static_assert((1 << DEC_NW_LOG) == DEC_NW, "1, 2, 4 or 8 waves");
 
-// DEC_PD = chunks in flight per wave = stages of the K and of the V ring: 2 (128 KiB of LDS, one workgroup per CU) or 1 (64 KiB, two
-// workgroups per CU: twice the waves, half the run-ahead each)
-template <int DH, int DEC_PD>
+// DEC_PD = chunks in flight per wave = stages of the K and of the V ring: ONE (64 KiB of LDS per workgroup, two workgroups per CU).
+// Measured on the same box at a 49 k context 326.2 tokens/s against 323.7 with two stages (128 KiB, one workgroup per CU; 64 splits;
+// 325.6 / 315.5 at 128), and 11.53 against 11.47 ms on the 26-sequence caption step - the run-ahead of a second stage buys nothing once
+// the stream is all-DMA (profiles/r05_run_i_*)
+constexpr int DEC_PD = 1;
+template <int DH>
 __global__ __launch_bounds__(64 * DEC_NW) void k_attn_decode(const _Float16* __restrict__ Q, int ldq, const _Float16* __restrict__ Kp, int ldk,
                                                         const _Float16* __restrict__ Vp, int ldv, int Sq, int Skv, int Hq, int Hkv, float scale_log2,
                                                         const int* __restrict__ kv_len, float* __restrict__ part, int nsplit, int q_hs, long q_bs,
@@ -369,22 +369,9 @@ void sc_attn_combine_launch(int Dh, const float* part, void* out, int ldo, int B
 
 void sc_attn_decode_launch(const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, int B, int Sq, int Skv, int Hq, int Hkv, float scale_log2,
                            const int32_t* kv_len, float* part, int nsplit, int q_hs, long q_bs, hipStream_t s) {
-    // SC_DEC_PD=1|2 pins the ring depth (A/B runs).  Default ONE stage per ring (64 KiB per workgroup): measured on the same box at a 49 k
-    // context 326.2 tokens/s against 323.7 with two stages (64 splits; 325.6 / 315.5 at 128), and 11.53 against 11.47 ms on the 26-sequence
-    // caption step - the run-ahead of a second stage buys nothing once the stream is all-DMA (profiles/r05_run_i_*)
-    static std::atomic<int> pd_env{-1};
-    if (pd_env < 0) { const char* e = getenv("SC_DEC_PD"); pd_env = e ? atoi(e) : 0; }
-    const int pd = (pd_env == 1 || pd_env == 2) ? pd_env.load() : 1;
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    auto go = [&](auto pdc) {
-        constexpr int PD = decltype(pdc)::value;
-        constexpr int LDS_RING = DEC_NW * 2 * PD * DCH * 128 * 2, LDS_MERGE = DEC_NW * (128 * 16 + 32) * 4;   // NW waves x (K ring + V ring) x PD stages of 8 KiB
-        constexpr int LDS_DEC = LDS_RING > LDS_MERGE ? LDS_RING : LDS_MERGE;
-        static std::atomic<bool> attr_done[16];
-        if (!attr_done[dev & 15]) { (void)hipFuncSetAttribute((const void*)k_attn_decode<128, PD>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_DEC); attr_done[dev & 15] = true; }
-        hipLaunchKernelGGL((k_attn_decode<128, PD>), dim3((unsigned)nsplit, (unsigned)Hq, (unsigned)B), dim3(64 * DEC_NW), LDS_DEC, s, (const _Float16*)q, ldq, (const _Float16*)k, ldk,
-                           (const _Float16*)v, ldv, Sq, Skv, Hq, Hkv, scale_log2, kv_len, part, nsplit, q_hs, q_bs, Hq / Hkv);
-    };
-    if (pd == 1) go(std::integral_constant<int, 1>{}); else go(std::integral_constant<int, 2>{});
+    constexpr int LDS_RING = DEC_NW * 2 * DEC_PD * DCH * 128 * 2, LDS_MERGE = DEC_NW * (128 * 16 + 32) * 4;   // NW waves x (K ring + V ring) x DEC_PD stages of 8 KiB
+    constexpr int LDS_DEC = LDS_RING > LDS_MERGE ? LDS_RING : LDS_MERGE;
+    sc_set_max_lds<k_attn_decode<128>>(LDS_DEC);
+    hipLaunchKernelGGL((k_attn_decode<128>), dim3((unsigned)nsplit, (unsigned)Hq, (unsigned)B), dim3(64 * DEC_NW), LDS_DEC, s, (const _Float16*)q, ldq, (const _Float16*)k, ldk,
+                       (const _Float16*)v, ldv, Sq, Skv, Hq, Hkv, scale_log2, kv_len, part, nsplit, q_hs, q_bs, Hq / Hkv);
 }

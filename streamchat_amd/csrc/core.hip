@@ -37,11 +37,22 @@ extern "C" int sc_device_info(int* cu_count, int* is_gfx950, size_t* hbm_bytes) 
 // (recorded when it is created), so two host threads driving two partitions never share a process-wide setting (round 5: the reader / updater
 // and the QA thread of streamchat_amd/session.py).  (ABI 7 removed the process-wide sc_set_cu_budget: the table below is the only source.)
 // One 64-bit word per slot - stream pointer's low 48 bits | CU count << 48 - so a reader never pairs a stream with another stream's count.
-#include <atomic>
 static constexpr int SC_MAX_MASKED = 32;
 static std::atomic<unsigned long long> g_masked[SC_MAX_MASKED];
 static inline unsigned long long sc_pack_masked(const void* s, int cus) { return ((unsigned long long)(uintptr_t)s & 0xFFFFFFFFFFFFull) | ((unsigned long long)cus << 48); }
-int sc_launch_cu_count(int device_cus, hipStream_t stream) {
+int sc_device_cu_count() {
+    static std::atomic<int> cached[16];
+    int dev = 0, n = 0;
+    if (hipGetDevice(&dev) != hipSuccess) return 256;
+    std::atomic<int>& c = cached[dev & 15];
+    if ((n = c.load(std::memory_order_relaxed)) > 0) return n;
+    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) return 256;
+    c.store(n, std::memory_order_relaxed);
+    return n;
+}
+
+int sc_launch_cu_count(hipStream_t stream) {
+    const int device_cus = sc_device_cu_count();
     int n = 0;
     if (stream)
         for (int i = 0; i < SC_MAX_MASKED; ++i) {

@@ -208,28 +208,21 @@ __device__ __forceinline__ void lds_load16(const void* base, unsigned extent, ch
     __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (__attribute__((address_space(3))) void*)lds, 16, (int)voff, (int)soff, 0, 0);
 }
 
-// WR = wave rows: 2 -> 256x256 tile, 8 waves, 4-slot ring (128 KiB, one workgroup per CU, DMA 3 steps ahead);
-//                  1 -> 128x256 tile, 4 waves, 3-slot ring (72 KiB, TWO workgroups per CU, DMA 2 steps ahead): for short-K GEMMs
-//                       (ViT, K = 1024: 32 steps) one workgroup's prologue / epilogue then overlaps the other's main loop.
-// PERSIST: the grid is one workgroup per CU and every workgroup walks tiles vb = blockIdx.x, + gridDim.x, ... (same tile order and
-//          XCD affinity as the one-tile-per-workgroup launch).  The K-step ring simply continues across the tile boundary: the DMA
-//          issued DIST steps ahead in the last steps of a tile fetches the first steps of the NEXT tile, so its data lands while the
-//          epilogue (no LDS) stores the finished tile, and the next tile starts without the ~2 us cold prologue (K = 1024: 32 steps
-//          per tile, the prologue was ~9 % of a tile).
-template <int EPI, bool OUT_F32, int WR, bool PERSIST = false>
-__global__ __launch_bounds__(WR * 256, 2) void k_gemm256(const _Float16* __restrict__ A, int lda, const _Float16* __restrict__ W,
+// One 256x256 tile per workgroup, 8 waves, SC_GEMM_NS-slot ring (one workgroup per CU, DMA NS - 1 steps ahead).
+template <int EPI, bool OUT_F32>
+__global__ __launch_bounds__(512, 2) void k_gemm256(const _Float16* __restrict__ A, int lda, const _Float16* __restrict__ W,
                                                          const _Float16* __restrict__ bias, const _Float16* __restrict__ R, int ldr,
                                                          void* __restrict__ Cout, int ldc, int M, int N, int K, int tilesN, int a_grp,
-                                                         int a_grp_stride, int a_grp_off, int GM, int ntiles) {
+                                                         int a_grp_stride, int a_grp_off, int GM) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    constexpr int NT = WR * 256;                    // threads
-    constexpr int NS = WR == 2 ? SC_GEMM_NS : 3;    // ring slots
+    constexpr int NT = 512;                         // threads
+    constexpr int NS = SC_GEMM_NS;                  // ring slots
     constexpr int DIST = NS - 1;                    // DMA issue distance in K-steps
-    constexpr int BMx = 128 * WR;
-    constexpr int AH = BMx * BK2 * 2;               // A bytes per stage
-    constexpr int STG = AH + HALF2;                 // + W bytes per stage (256 rows)
-    constexpr int GW = 4 / WR;                      // W granules per thread per stage (A: always 2)
-    const int nwg = PERSIST ? ntiles : (int)gridDim.x;
+    constexpr int BMx = BM2;
+    constexpr int AH = HALF2;                       // A bytes per stage
+    constexpr int STG = STAGE2;                     // + W bytes per stage (256 rows)
+    constexpr int GW = 2;                           // W granules per thread per stage (A: 2 as well)
+    const int nwg = (int)gridDim.x;
     auto tile_of = [&](int bid, int& tm_, int& tn_) {
         const int xcd = bid & 7, q8 = nwg >> 3, r8 = nwg & 7;
         const int swz = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
@@ -239,8 +232,8 @@ __global__ __launch_bounds__(WR * 256, 2) void k_gemm256(const _Float16* __restr
         const int gm = (tilesM - grp * GM) < GM ? (tilesM - grp * GM) : GM;
         tm_ = grp * GM + within % gm; tn_ = within / gm;
     };
-    int vb = blockIdx.x, tm, tn;
-    tile_of(vb, tm, tn);
+    int tm, tn;
+    tile_of(blockIdx.x, tm, tn);
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -249,15 +242,6 @@ __global__ __launch_bounds__(WR * 256, 2) void k_gemm256(const _Float16* __restr
     // staging: granule q = j*NT + tid -> row q>>2, physical slot q&3
     const _Float16* a_src[2];
     const _Float16* w_src[GW];
-    // PERSIST: no per-lane pointers at all - constant per-lane 32-bit offsets inside a tile + uniform (SGPR) tile / K-step offsets
-    // through buffer_load ... lds; rows >= M are out of the resource's extent and arrive as zeros (they are never stored).
-    unsigned a_vo[2], w_vo[GW];
-#pragma unroll
-    for (int j = 0; j < 2; ++j) { const int q = j * NT + tid, r = q >> 2; a_vo[j] = ((unsigned)r * (unsigned)lda + (unsigned)(((q & 3) ^ swzF(r >> 2)) * 8)) * 2u; }
-#pragma unroll
-    for (int j = 0; j < GW; ++j) { const int q = j * NT + tid, r = q >> 2; w_vo[j] = ((unsigned)r * (unsigned)K + (unsigned)(((q & 3) ^ swzF(r >> 2)) * 8)) * 2u; }
-    const unsigned a_ext = (unsigned)M * (unsigned)lda * 2u, w_ext = (unsigned)N * (unsigned)K * 2u;
-    int tm_nx = 0, tn_nx = 0;                       // PERSIST: next tile of this workgroup
     auto set_src = [&](int tm_, int tn_, const _Float16* (&as)[2], const _Float16* (&ws)[GW]) {
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
@@ -277,36 +261,20 @@ __global__ __launch_bounds__(WR * 256, 2) void k_gemm256(const _Float16* __restr
             ws[j] = W + (size_t)(tn_ * BN2 + r) * (size_t)K + sl * 8;
         }
     };
-    if (!PERSIST) set_src(tm, tn, a_src, w_src);
+    set_src(tm, tn, a_src, w_src);
     const int nk = K / BK2;
-    int sb = 0;                                     // ring slot of K-step 0 of the current tile (PERSIST: the ring runs on across tiles)
-    bool has_next = false;
-    auto slot_of = [&](int ks) { return NS == 4 ? ((sb + ks) & 3) : ((sb + ks) % NS); };
+    auto slot_of = [&](int ks) { return NS == 4 ? (ks & 3) : (ks % NS); };
     auto issue_w = [&](int ks) {
         char* base = smem + slot_of(ks) * STG + AH;
-        if (PERSIST) {
-            const bool nx = ks >= nk;                // wave-uniform: the step belongs to the next tile
-            const unsigned so = ((unsigned)(nx ? tn_nx : tn) * (unsigned)(BN2 * K) + (unsigned)((nx ? ks - nk : ks) * BK2)) * 2u;
 #pragma unroll
-            for (int j = 0; j < GW; ++j) lds_load16(W, w_ext, base + (j * NT + wave * 64) * 16, w_vo[j], so);
-        } else {
-#pragma unroll
-            for (int j = 0; j < GW; ++j)
-                __builtin_amdgcn_global_load_lds((glb_ptr_t)(w_src[j] + ks * BK2), (lds_ptr_t)(base + (j * NT + wave * 64) * 16), 16, 0, 0);
-        }
+        for (int j = 0; j < GW; ++j)
+            __builtin_amdgcn_global_load_lds((glb_ptr_t)(w_src[j] + ks * BK2), (lds_ptr_t)(base + (j * NT + wave * 64) * 16), 16, 0, 0);
     };
     auto issue_a = [&](int ks) {
         char* base = smem + slot_of(ks) * STG;
-        if (PERSIST) {
-            const bool nx = ks >= nk;
-            const unsigned so = ((unsigned)(nx ? tm_nx : tm) * (unsigned)(BMx * lda) + (unsigned)((nx ? ks - nk : ks) * BK2)) * 2u;
 #pragma unroll
-            for (int j = 0; j < 2; ++j) lds_load16(A, a_ext, base + (j * NT + wave * 64) * 16, a_vo[j], so);
-        } else {
-#pragma unroll
-            for (int j = 0; j < 2; ++j)
-                __builtin_amdgcn_global_load_lds((glb_ptr_t)(a_src[j] + ks * BK2), (lds_ptr_t)(base + (j * NT + wave * 64) * 16), 16, 0, 0);
-        }
+        for (int j = 0; j < 2; ++j)
+            __builtin_amdgcn_global_load_lds((glb_ptr_t)(a_src[j] + ks * BK2), (lds_ptr_t)(base + (j * NT + wave * 64) * 16), 16, 0, 0);
     };
     // wait until at most `steps_in_flight` K-steps of this thread's DMA are outstanding (2 + GW issues per step)
     auto wait_steps = [&](int steps_in_flight) {
@@ -314,15 +282,6 @@ __global__ __launch_bounds__(WR * 256, 2) void k_gemm256(const _Float16* __restr
         else if (steps_in_flight == 1) { if (GW == 2) asm volatile("s_waitcnt vmcnt(4)" ::: "memory"); else asm volatile("s_waitcnt vmcnt(6)" ::: "memory"); }
         else { if (GW == 2) asm volatile("s_waitcnt vmcnt(8)" ::: "memory"); else asm volatile("s_waitcnt vmcnt(12)" ::: "memory"); }
     };
-
-    // PERSIST, first two K-steps after an epilogue: the loads being waited for (issued before the epilogue) are OLDER than the
-    // epilogue's 16 (SwiGLU: 8) global stores, which share vmcnt on gfx9 - allow those stores (and the one younger DMA step) to stay
-    // in flight, otherwise the wave stalls until its C tile has reached memory and the stores never overlap the next tile's MFMAs.
-    auto wait_after_epilogue = [&]() {
-        constexpr int CNT = (EPI == SC_EPI_SWIGLU ? 8 : 16) + (DIST - 2) * (2 + GW);
-        asm volatile("s_waitcnt vmcnt(%0)" ::"n"(CNT) : "memory");
-    };
-    int relax = 0;                                  // K-steps left that may use it (0 after an edge tile: fewer stores were issued)
 
     const int rl = lane & 15, g = lane >> 4;
     const int frag = rl * 64 + ((g ^ swzF(rl >> 2)) << 4);
@@ -361,7 +320,7 @@ __global__ __launch_bounds__(WR * 256, 2) void k_gemm256(const _Float16* __restr
             for (int j = 0; j < 4; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(bc[j], alo[i], acc[i][j], 0, 0, 0);
         if (SC_GEMM_SETPRIO) __builtin_amdgcn_s_setprio(0);
         // step ks+1 must have landed for everyone (steps ks+2 .. ks+DIST-1 may stay in flight); slot of step ks-1 is free afterwards
-        if (steady) { if (decltype(sid)::value >= 7) wait_after_epilogue(); else wait_steps(DIST - 2); }
+        if (steady) wait_steps(DIST - 2);
         else { const int newest = (ks + DIST - 1) < (nk - 1) ? (ks + DIST - 1) : (nk - 1); wait_steps(newest - (ks + 1)); }
         __builtin_amdgcn_s_barrier();
         if (steady) { issue_w(ks + DIST); issue_a(ks + DIST); }
@@ -388,23 +347,7 @@ __global__ __launch_bounds__(WR * 256, 2) void k_gemm256(const _Float16* __restr
             for (int i = 0; i < (12 - (GW - 2)) / SC_GEMM_MPL; ++i) { __builtin_amdgcn_sched_group_barrier(0x008, 1, SID); __builtin_amdgcn_sched_group_barrier(0x100, SC_GEMM_MPL, SID); }
         }
     };
-    for (;;) {                                           // PERSIST: tiles of this workgroup; otherwise exactly one pass
-    if (PERSIST) {
-        has_next = vb + (int)gridDim.x < ntiles;
-        if (has_next) tile_of(vb + gridDim.x, tm_nx, tn_nx);
-    }
     int ks = 0;
-    if (PERSIST && has_next) {
-        if (relax) {                                     // first pair after a full tile's epilogue: its stores may stay in flight
-            kstep(std::integral_constant<int, 7>{}, 0, true, aloA, ahiA, bcA, aloB, ahiB, bcB);
-            kstep(std::integral_constant<int, 8>{}, 1, true, aloB, ahiB, bcB, aloA, ahiA, bcA);
-            ks = 2;
-        }
-        for (; ks + 1 < nk; ks += 2) {                   // every step is steady: steps >= nk of the issue stream are the next tile's
-            kstep(std::integral_constant<int, 5>{}, ks, true, aloA, ahiA, bcA, aloB, ahiB, bcB);
-            kstep(std::integral_constant<int, 6>{}, ks + 1, true, aloB, ahiB, bcB, aloA, ahiA, bcA);
-        }
-    } else {
     for (; ks + 1 + DIST < nk; ks += 2) {                // steady state: both steps of the pair still issue DMA
         kstep(std::integral_constant<int, 0>{}, ks, true, aloA, ahiA, bcA, aloB, ahiB, bcB);
         kstep(std::integral_constant<int, 1>{}, ks + 1, true, aloB, ahiB, bcB, aloA, ahiA, bcA);
@@ -414,7 +357,6 @@ __global__ __launch_bounds__(WR * 256, 2) void k_gemm256(const _Float16* __restr
         kstep(std::integral_constant<int, 3>{}, ks + 1, false, aloB, ahiB, bcB, aloA, ahiA, bcA);
     }
     if (ks < nk) kstep(std::integral_constant<int, 4>{}, ks, false, aloA, ahiA, bcA, aloB, ahiB, bcB);
-    }
 
     // ---- epilogue.  Each lane owns C[m = m0 + mi*16 + rl][n0 + nj*16 + g*4 .. +3]; bias / activation / residual are applied in
     // fp32 in that ownership.  The fp16 results are then exchanged between the four 16-lane rows of the wave with
@@ -511,17 +453,6 @@ __global__ __launch_bounds__(WR * 256, 2) void k_gemm256(const _Float16* __restr
                 }
             }
         }
-    }
-    if (!PERSIST || !has_next) break;
-    // next tile of this workgroup: its first DIST steps are already in flight and its step-0 fragments are in set A (nk is even)
-#pragma unroll
-    for (int i = 0; i < 8; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc[i][j] = sc_f4{0.f, 0.f, 0.f, 0.f};
-    relax = (tm * BMx + BMx <= M) ? 2 : 0;          // full tile: every lane issued all its stores
-    vb += gridDim.x;
-    tm = tm_nx; tn = tn_nx;
-    sb = (sb + nk) % NS;
     }
 }
 
@@ -880,7 +811,7 @@ __global__ __launch_bounds__(256, 1) void k_gemm_fat(const _Float16* __restrict_
             // the 16-column tile nj with nj + 4 of the SAME lane.  x' = (x_j cos - x_{j+64} sin, x_{j+64} cos + x_j sin) on the fp32
             // accumulators + bias with the fp32 table row of the token's position (row m -> position pos0 + m; [cos(64) | sin(64)], the
             // query table pre-multiplied by the softmax scale * log2 e), rounded to fp16 once.  Same arithmetic as k_rope_f32in
-            // (llm_ops.hip) and k_decode_qkv<true> (gemv.hip).
+            // (llm_ops.hip) and k_decode_qkv (gemv.hip).
             const __amdgpu_buffer_rsrc_t rs_t = uniform_rsrc(tab + (size_t)(pos0 + m0) * 128, rv * 512);
             int rstep_t = 16 * 512;
             asm volatile("" : "+v"(rstep_t));
@@ -1080,212 +1011,9 @@ __global__ __launch_bounds__(256) void k_gemm_skinny(const _Float16* __restrict_
     }
 }
 
-// Round 5: k_gemm_skinny for K known at compile time (the Qwen2-7B widths 3584 and 18944): the K-quarter of a wave is straight-line
-// code in batches of BT k-steps with two register buffers.  In the run-time loop above hipcc requests the activation fragments BEHIND
-// the weights they multiply (vmcnt retires in order: the first MFMA of a batch waits for the whole batch and then for an L2 round
-// trip), consumes a batch before it requests the next one, and peels the trip % 8 remainder into one-k-step trips - the batched
-// caption decode (26 sequences) ran its projections at 1.7 - 2.5 TB/s (profiles/r05_*).  Here the queue of a wave is
-//   [x fragments of batch 0] [W of batch 0] | per batch b: [x of b + 1] [W of b + 1]  ->  MFMAs of batch b
-// (x first: it comes out of L2 and is back long before the weights), same k order per accumulator as the loop above: the sums are
-// bit-identical to k_gemm_skinny's.
-template <int EPI, bool OUT_F32, int MG, int KW, int BT>      // KW = k-steps (of 32) per wave = K / 4 / 32
-__global__ __launch_bounds__(256) void k_gemm_skinny_u(const _Float16* __restrict__ A, int lda, const _Float16* __restrict__ W,
-                                                       const _Float16* __restrict__ bias, const _Float16* __restrict__ R, int ldr,
-                                                       void* __restrict__ Cout, int ldc, int M, int N) {
-    constexpr int K = KW * 32 * 4, NB = (KW + BT - 1) / BT;
-    __shared__ float red[3][MG][4][64];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int rl = lane & 15, g = lane >> 4;
-    const int n0 = blockIdx.x * 16;
-    const int k_lo = wave * (K / 4);
-    const _Float16* wp = W + (size_t)(n0 + rl) * (size_t)K + k_lo + g * 8;
-    const _Float16* xp[MG];
-#pragma unroll
-    for (int mg = 0; mg < MG; ++mg) {
-        int m = mg * 16 + rl;
-        m = m < M ? m : M - 1;
-        xp[mg] = A + (size_t)m * (size_t)lda + k_lo + g * 8;
-    }
-    sc_f4 acc[MG];
-#pragma unroll
-    for (int mg = 0; mg < MG; ++mg) acc[mg] = sc_f4{0.f, 0.f, 0.f, 0.f};
-    sc_h8 wf[2][BT], xf[2][BT][MG];
-    auto load = [&](auto bc) {
-        constexpr int B = decltype(bc)::value;
-#pragma unroll
-        for (int u = 0; u < BT; ++u)
-            if (B * BT + u < KW) {
-#pragma unroll
-                for (int mg = 0; mg < MG; ++mg) xf[B & 1][u][mg] = *reinterpret_cast<const sc_h8*>(xp[mg] + (B * BT + u) * 32);
-            }
-#pragma unroll
-        for (int u = 0; u < BT; ++u)
-            if (B * BT + u < KW) wf[B & 1][u] = __builtin_nontemporal_load(reinterpret_cast<const sc_h8*>(wp + (B * BT + u) * 32));
-    };
-    auto run = [&](auto self, auto bc) -> void {
-        constexpr int B = decltype(bc)::value;
-        if constexpr (B < NB) {
-            if constexpr (B + 1 < NB) load(std::integral_constant<int, B + 1>{});
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int u = 0; u < BT; ++u)
-                if (B * BT + u < KW) {
-#pragma unroll
-                    for (int mg = 0; mg < MG; ++mg) acc[mg] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wf[B & 1][u], xf[B & 1][u][mg], acc[mg], 0, 0, 0);
-                }
-            __builtin_amdgcn_sched_barrier(0);
-            self(self, std::integral_constant<int, B + 1>{});
-        }
-    };
-    load(std::integral_constant<int, 0>{});
-    run(run, std::integral_constant<int, 0>{});
-    if (wave > 0) {
-#pragma unroll
-        for (int mg = 0; mg < MG; ++mg)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) red[wave - 1][mg][r][lane] = acc[mg][r];
-    }
-    __syncthreads();
-    if (wave > 0) return;
-    const int n = n0 + g * 4;
-#pragma unroll
-    for (int mg = 0; mg < MG; ++mg) {
-        float v[4];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) v[r] = acc[mg][r] + red[0][mg][r][lane] + red[1][mg][r][lane] + red[2][mg][r][lane] + (bias ? (float)bias[n + r] : 0.f);
-        const int m = mg * 16 + rl;
-        if (m >= M) continue;
-        if (EPI == SC_EPI_SWIGLU) {
-            const float o0 = v[0] / (1.0f + __expf(-v[0])) * v[2], o1 = v[1] / (1.0f + __expf(-v[1])) * v[3];
-            const sc_h2 o = {(_Float16)o0, (_Float16)o1};
-            *reinterpret_cast<sc_h2*>(reinterpret_cast<_Float16*>(Cout) + (size_t)m * (size_t)ldc + (n >> 1)) = o;
-        } else {
-#pragma unroll
-            for (int r = 0; r < 4; ++r) v[r] = epi_apply(v[r], EPI);
-            if (R) { const sc_h4 r4 = *reinterpret_cast<const sc_h4*>(R + (size_t)m * (size_t)ldr + n); for (int r = 0; r < 4; ++r) v[r] += (float)r4[r]; }
-            if (OUT_F32) *reinterpret_cast<sc_f4*>(reinterpret_cast<float*>(Cout) + (size_t)m * (size_t)ldc + n) = sc_f4{v[0], v[1], v[2], v[3]};
-            else *reinterpret_cast<sc_h4*>(reinterpret_cast<_Float16*>(Cout) + (size_t)m * (size_t)ldc + n) = sc_h4{(_Float16)v[0], (_Float16)v[1], (_Float16)v[2], (_Float16)v[3]};
-        }
-    }
-}
-
-// Round 5: the batched-decode projection for K = 3584 (Qwen2-7B hidden width) with the ACTIVATIONS RESIDENT IN REGISTERS.
-// k_gemm_skinny(_u) re-reads the M x K activation block from L2 for every strip of 16 weight rows: at 26 rows that is twice the bytes of
-// the weights themselves through the texture path (gate/up: 543 MB of x for 271 MB of W), and the weight stream stood at 2.3 - 2.9
-// TB/s.  Here a workgroup is persistent over a contiguous range of strips (even shares of N / 16 over the CUs); wave w keeps the
-// MFMA B fragments of x[:, w * 896 : (w + 1) * 896] - 28 k-steps x MG fragments = 224 VGPRs at MG = 2, one wave per SIMD owns the
-// whole 512-register file - for its lifetime, and per strip streams ONLY weights: 28 x 16 B per lane, all requested at once, two
-// register buffers so that strip s + 1 is in flight while strip s is multiplied and reduced (4 waves = 4 K-quarters, partial tiles
-// through a double-buffered LDS scratch, one barrier per strip; wave 0 applies the epilogue).  Everything a strip's epilogue reads
-// (bias, residual) is requested BEFORE the next strip's weights, so that no wait ever drains the weight queue.  Same k order per
-// accumulator and same cross-wave sum as k_gemm_skinny: bit-identical results.
-template <int EPI, bool OUT_F32, int MG>
-__global__ __launch_bounds__(256) void k_gemm_skinny_x(const _Float16* __restrict__ A, int lda, const _Float16* __restrict__ W,
-                                                       const _Float16* __restrict__ bias, const _Float16* __restrict__ R, int ldr,
-                                                       void* __restrict__ Cout, int ldc, int M, int N, int strips_q, int strips_r) {
-    constexpr int KW = 28, K = KW * 32 * 4;
-    __shared__ float red[2][3][MG][4][64];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int rl = lane & 15, g = lane >> 4;
-    const int k_lo = wave * (K / 4);
-    const int b = blockIdx.x;
-    const int s_lo = b * strips_q + min(b, strips_r), s_hi = s_lo + strips_q + (b < strips_r ? 1 : 0);      // the first strips_r workgroups take one strip more
-    if (s_lo >= s_hi) return;
-    sc_h8 xf[KW][MG];
-#pragma unroll
-    for (int mg = 0; mg < MG; ++mg) {
-        int m = mg * 16 + rl;
-        m = m < M ? m : M - 1;
-        const _Float16* xp = A + (size_t)m * (size_t)lda + k_lo + g * 8;
-#pragma unroll
-        for (int u = 0; u < KW; ++u) xf[u][mg] = *reinterpret_cast<const sc_h8*>(xp + u * 32);
-    }
-    const _Float16* wbase = W + (size_t)rl * (size_t)K + k_lo + g * 8;
-    sc_h8 wa[KW], wb[KW];
-    sc_h4 ba, bb, ra[MG], rb[MG];
-    auto load_w = [&](sc_h8 (&buf)[KW], int strip) {
-        const _Float16* wp = wbase + (size_t)strip * (size_t)(16 * K);
-#pragma unroll
-        for (int u = 0; u < KW; ++u) buf[u] = __builtin_nontemporal_load(reinterpret_cast<const sc_h8*>(wp + u * 32));
-    };
-    auto load_e = [&](sc_h4& bv, sc_h4 (&rv)[MG], int strip) {          // what the epilogue of `strip` adds (null pointers read W / A: dropped)
-        const int n = strip * 16 + g * 4;
-        bv = *reinterpret_cast<const sc_h4*>(bias ? bias + n : W);
-#pragma unroll
-        for (int mg = 0; mg < MG; ++mg) {
-            int m = mg * 16 + rl;
-            m = m < M ? m : M - 1;
-            rv[mg] = *reinterpret_cast<const sc_h4*>(R ? R + (size_t)m * (size_t)ldr + n : A);
-        }
-    };
-    auto compute = [&](const sc_h8 (&buf)[KW], const sc_h4& bv, const sc_h4 (&rv)[MG], int strip) {
-        sc_f4 acc[MG];
-#pragma unroll
-        for (int mg = 0; mg < MG; ++mg) acc[mg] = sc_f4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int u = 0; u < KW; ++u)
-#pragma unroll
-            for (int mg = 0; mg < MG; ++mg) acc[mg] = __builtin_amdgcn_mfma_f32_16x16x32_f16(buf[u], xf[u][mg], acc[mg], 0, 0, 0);
-        float (*rd)[MG][4][64] = red[strip & 1];
-        if (wave > 0) {
-#pragma unroll
-            for (int mg = 0; mg < MG; ++mg)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) rd[wave - 1][mg][r][lane] = acc[mg][r];
-        }
-        __syncthreads();
-        if (wave > 0) return;
-        const int n = strip * 16 + g * 4;
-#pragma unroll
-        for (int mg = 0; mg < MG; ++mg) {
-            float v[4];
-#pragma unroll
-            for (int r = 0; r < 4; ++r) v[r] = acc[mg][r] + rd[0][mg][r][lane] + rd[1][mg][r][lane] + rd[2][mg][r][lane] + (bias ? (float)bv[r] : 0.f);
-            const int m = mg * 16 + rl;
-            if (m >= M) continue;
-            if (EPI == SC_EPI_SWIGLU) {
-                const float o0 = v[0] / (1.0f + __expf(-v[0])) * v[2], o1 = v[1] / (1.0f + __expf(-v[1])) * v[3];
-                const sc_h2 o = {(_Float16)o0, (_Float16)o1};
-                *reinterpret_cast<sc_h2*>(reinterpret_cast<_Float16*>(Cout) + (size_t)m * (size_t)ldc + (n >> 1)) = o;
-            } else {
-#pragma unroll
-                for (int r = 0; r < 4; ++r) v[r] = epi_apply(v[r], EPI);
-                if (R) { for (int r = 0; r < 4; ++r) v[r] += (float)rv[mg][r]; }
-                if (OUT_F32) *reinterpret_cast<sc_f4*>(reinterpret_cast<float*>(Cout) + (size_t)m * (size_t)ldc + n) = sc_f4{v[0], v[1], v[2], v[3]};
-                else *reinterpret_cast<sc_h4*>(reinterpret_cast<_Float16*>(Cout) + (size_t)m * (size_t)ldc + n) = sc_h4{(_Float16)v[0], (_Float16)v[1], (_Float16)v[2], (_Float16)v[3]};
-            }
-        }
-    };
-    int st = s_lo;
-    load_e(ba, ra, st);
-    load_w(wa, st);
-    while (st + 2 < s_hi) {                // strips st and st + 1 are processed in this trip; st + 2 exists: no load sits behind a condition
-        // (the scheduling fences keep the next strip's loads AHEAD of this strip's MFMAs: left alone, hipcc sinks them below the MFMAs to
-        //  reuse the registers they free - one buffer instead of two, and every strip starts with a full memory round trip)
-        load_e(bb, rb, st + 1); load_w(wb, st + 1);
-        __builtin_amdgcn_sched_barrier(0);
-        compute(wa, ba, ra, st);
-        __builtin_amdgcn_sched_barrier(0);
-        load_e(ba, ra, st + 2); load_w(wa, st + 2);
-        __builtin_amdgcn_sched_barrier(0);
-        compute(wb, bb, rb, st + 1);
-        __builtin_amdgcn_sched_barrier(0);
-        st += 2;
-    }
-    if (st + 1 < s_hi) {
-        load_e(bb, rb, st + 1); load_w(wb, st + 1);
-        __builtin_amdgcn_sched_barrier(0);
-        compute(wa, ba, ra, st);
-        __builtin_amdgcn_sched_barrier(0);
-        compute(wb, bb, rb, st + 1);
-    } else {
-        compute(wa, ba, ra, st);
-    }
-}
-
 // ------------------------------------------------------------------------------------------------------------------
 // Round 5: the skinny GEMM with BOTH operands staged through per-wave LDS rings by LDS-DMA (k_gemm_skinny_l).
-// What bounds the register-operand kernels above is not HBM and not occupancy (8 / 16 waves per strip change nothing,
+// What bounds the register-operand kernel above (k_gemm_skinny) is not HBM and not occupancy (8 / 16 waves per strip change nothing,
 // profiles/r05_run_k_*) but the CU's address path: the MFMA A / B operand layout makes lane (rl, g) read 16 bytes of ROW rl at k-chunk g, so
 // the 16 lanes of a quarter-wave touch 16 different rows - every `global_load_dwordx4` is 64 separate cache-line lookups of 16 bytes
 // each, against 8 for a coalesced 1 KiB.  At one line per clock that IS the measured time of the 3584-row projections of the batched
@@ -1430,7 +1158,7 @@ __global__ __launch_bounds__(256) void k_gemm_skinny_l(const _Float16* __restric
 }
 
 // k_gemm_skinny_l for the MANY-strip shapes of K = 3584 (gate/up, lm_head): the activations stay resident in registers for the lifetime of the
-// workgroup as in k_gemm_skinny_x (one fetch per WORKGROUP instead of one per strip), only the weights run through the per-wave LDS ring -
+// workgroup (one fetch per WORKGROUP instead of one per strip), only the weights run through the per-wave LDS ring -
 // 8 stages of 4 KiB: 28 KiB of weight requests in flight per wave.  Same operands, same order: bit-identical to the other skinny kernels.
 template <int EPI, bool OUT_F32, int MG>
 __global__ __launch_bounds__(256) void k_gemm_skinny_lx(const _Float16* __restrict__ A, int lda, const _Float16* __restrict__ W,
@@ -1546,88 +1274,79 @@ __global__ __launch_bounds__(256) void k_gemm_skinny_lx(const _Float16* __restri
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 }
 
+// raster group of the 256x256-tile kernels: GM tile-rows, 4 for wide N (A/B in profiles/)
+constexpr int raster_group(int tilesN) { return tilesN > 16 ? 4 : SC_GEMM_GM; }
+
+// k_gemm_fat, for sc_gemm_f16 and sc_gemm_headed_f16: one tile per workgroup, or a persistent walk (one workgroup per CU) once there
+// are more tiles than CUs - the next tile's first iterations are then fetched under the epilogue of the current one (measured,
+// profiles/r01_run99: +2..4 % at K = 1024, -1..3.5 % at K >= 3584 where the per-tile epilogue is a small share).  A CU-masked stream
+// gets a persistent grid of its own size.
+template <int EPI, bool RES>
+int launch_fat(const void* A, int lda, const void* W, const void* bias, const void* R, int ldr, void* C, int ldc, int M, int N, int K,
+               const float* tab, int pos0, int lead_cols, float col_scale, hipStream_t s, const char* api) {
+    constexpr int LDS = 163840;
+    const int n_cu = sc_launch_cu_count(s), tN = N / BN2, nt_all = ((M + BM2 - 1) / BM2) * tN;
+    auto go = [&](auto persist, unsigned grid) {
+        constexpr bool P = decltype(persist)::value;
+        sc_set_max_lds<k_gemm_fat<EPI, P, RES>>(LDS);
+        hipLaunchKernelGGL((k_gemm_fat<EPI, P, RES>), dim3(grid), dim3(256), LDS, s, (const _Float16*)A, lda, (const _Float16*)W, (const _Float16*)bias,
+                           (const _Float16*)R, ldr, C, ldc, M, N, K, tN, raster_group(tN), nt_all, tab, pos0, lead_cols, col_scale);
+    };
+    if (nt_all > n_cu) go(std::true_type{}, (unsigned)n_cu);
+    else go(std::false_type{}, (unsigned)nt_all);
+    SC_CHECK_LAUNCH(api);
+    return SC_OK;
+}
+
+// SC_SKINNY_GENERIC=1 pins the run-time-loop k_gemm_skinny for every M <= 32 call (the reference path of tests/test_gpu_gemv_spec.py)
+bool skinny_generic() {
+    static const bool on = [] { const char* e = getenv("SC_SKINNY_GENERIC"); return e && e[0] == '1'; }();
+    return on;
+}
+
 template <int EPI>
 int launch_gemm(const void* A, int lda, const void* W, const void* bias, const void* R, int ldr, void* C, int ldc, int M, int N,
                 int K, int out_f32, int a_grp, int a_grp_stride, int a_grp_off, hipStream_t s) {
-    // hipFuncSetAttribute and the CU count are PER DEVICE: the flags below are indexed by the current device, so a process that drives
-    // several GPUs (the reference puts its two model replicas on cuda:0 / cuda:1) raises the LDS limit on each of them
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    dev &= 15;
-    static std::atomic<int> force{-1};                       // SC_GEMM_KERNEL=128|256 pins the variant (A/B benchmarking)
-    if (force < 0) { const char* e = getenv("SC_GEMM_KERNEL"); force = e ? atoi(e) : 0; }
-    if (force == 0 && M <= 32 && K % 128 == 0 && a_grp == 0 && ldc % 4 == 0 && (!R || ldr % 4 == 0)) {      // few rows: stream W once
-        const dim3 grid((unsigned)(N / 16)), block(256);
-        // both operands through LDS rings (k_gemm_skinny_l): K in whole 512-element quarters-of-stages; SC_SKINNY_LDS=0 pins the register-operand kernels
-        static std::atomic<int> lds_on{-1};
-        if (lds_on < 0) { const char* e = getenv("SC_SKINNY_LDS"), *gnr = getenv("SC_SKINNY_GENERIC"); lds_on = ((e && e[0] == '0') || (gnr && gnr[0] == '1')) ? 0 : 1; }
-        // (K >= 2048: a strip has at least PD stages per wave, so the epilogue buffer of strip s + 2 is requested after strip s has been stored)
-        // FEW strips only (N / 16 below two per CU: o, down, q|k|v, kv of the batched decode, the text encoders' K = 4096 projections).  Measured
-        // at M = 26, same box, us per launch LDS / register operands (profiles/r05_run_o_skinny_lds.md): q 7.9 / 11.8, kv 6.9 / 11.1, o 8.0 / 12.1,
-        // q|k|v 11.5 / 20.5, down 38.8 / 50.6 - but gate/up 67.4 / 59.6 and lm_head 268 / 231: with many strips per workgroup the x-resident
-        // register kernel (k_gemm_skinny_x) reads x once per WORKGROUP, this one once per strip (543 MB of x through LDS for 271 MB of weights)
-        static std::atomic<int> n_cu_l[16];
-        if (n_cu_l[dev] == 0) { int n = 0; n_cu_l[dev] = (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n > 0) ? n : 256; }
-        if constexpr (EPI == SC_EPI_NONE || EPI == SC_EPI_SWIGLU) if (lds_on && N / 16 < 2 * n_cu_l[dev] && K % 512 == 0 && K >= 2048 && lda % 8 == 0 && (!R || ldr % 8 == 0) &&
-                                                                        ((reinterpret_cast<uintptr_t>(A) | reinterpret_cast<uintptr_t>(W) | reinterpret_cast<uintptr_t>(R) | reinterpret_cast<uintptr_t>(bias)) & 15) == 0) {
-            const int strips = N / 16, cus = sc_launch_cu_count(n_cu_l[dev], s), gx = strips < cus ? strips : cus;
-            static std::atomic<bool> attr_done[16][8];
-#define SC_LSL(F32, MGV, PDV, SLOT) do { constexpr int LDSB = 4 * PDV * (4096 + MGV * 4096) + 3 * MGV * 4 * 64 * 4 + 2 * 2048;                                   \
-                SC_REQUIRE(K / 512 >= PDV, "sc_gemm_f16: k_gemm_skinny_l needs K / 512 >= %d stages per strip (its epilogue tile is double-buffered by strip parity)", PDV); \
-                if (!attr_done[dev][SLOT]) { (void)hipFuncSetAttribute((const void*)k_gemm_skinny_l<EPI, F32, MGV, PDV>, hipFuncAttributeMaxDynamicSharedMemorySize, LDSB); attr_done[dev][SLOT] = true; } \
-                hipLaunchKernelGGL((k_gemm_skinny_l<EPI, F32, MGV, PDV>), dim3((unsigned)gx), block, LDSB, s, (const _Float16*)A, lda, (const _Float16*)W,        \
-                                   (const _Float16*)bias, (const _Float16*)R, ldr, C, ldc, M, N, K, strips / gx, strips % gx); } while (0)
-            if (M <= 16) { if (out_f32) SC_LSL(true, 1, 4, 0); else SC_LSL(false, 1, 4, 1); }
-            else { if (out_f32) SC_LSL(true, 2, 3, 2); else SC_LSL(false, 2, 3, 3); }
+    if (M <= 32 && K % 128 == 0 && a_grp == 0 && ldc % 4 == 0 && (!R || ldr % 4 == 0)) {      // few rows: stream W once
+        const dim3 block(256);
+        // the LDS-ring kernels: 16-byte aligned operands and rows
+        const bool al16 = ((reinterpret_cast<uintptr_t>(A) | reinterpret_cast<uintptr_t>(W) | reinterpret_cast<uintptr_t>(R) | reinterpret_cast<uintptr_t>(bias)) & 15) == 0;
+        if constexpr (EPI == SC_EPI_NONE || EPI == SC_EPI_SWIGLU) if (!skinny_generic() && al16 && lda % 8 == 0 && (!R || ldr % 8 == 0)) {
+            const int strips = N / 16, dev_cus = sc_device_cu_count(), cus = sc_launch_cu_count(s);
+            // both operands through LDS rings (k_gemm_skinny_l): K in whole 512-element quarters-of-stages
+            // (K >= 2048: a strip has at least PD stages per wave, so the epilogue buffer of strip s + 2 is requested after strip s has been stored)
+            // FEW strips only (N / 16 below two per CU: o, down, q|k|v, kv of the batched decode, the text encoders' K = 4096 projections).  Measured
+            // at M = 26, same box, us per launch LDS / register operands (profiles/r05_run_o_skinny_lds.md): q 7.9 / 11.8, kv 6.9 / 11.1, o 8.0 / 12.1,
+            // q|k|v 11.5 / 20.5, down 38.8 / 50.6 - but gate/up 67.4 / 59.6 and lm_head 268 / 231: with many strips per workgroup the kernel below
+            // reads x once per WORKGROUP, this one once per strip (543 MB of x through LDS for 271 MB of weights)
+            if (strips < 2 * dev_cus && K % 512 == 0 && K >= 2048) {
+                const int gx = strips < cus ? strips : cus;
+#define SC_LSL(F32, MGV, PDV) do { constexpr int LDSB = 4 * PDV * (4096 + MGV * 4096) + 3 * MGV * 4 * 64 * 4 + 2 * 2048;                                    \
+                    SC_REQUIRE(K / 512 >= PDV, "sc_gemm_f16: k_gemm_skinny_l needs K / 512 >= %d stages per strip (its epilogue tile is double-buffered by strip parity)", PDV); \
+                    sc_set_max_lds<k_gemm_skinny_l<EPI, F32, MGV, PDV>>(LDSB);                                                                                   \
+                    hipLaunchKernelGGL((k_gemm_skinny_l<EPI, F32, MGV, PDV>), dim3((unsigned)gx), block, LDSB, s, (const _Float16*)A, lda, (const _Float16*)W,   \
+                                       (const _Float16*)bias, (const _Float16*)R, ldr, C, ldc, M, N, K, strips / gx, strips % gx); } while (0)
+                if (M <= 16) { if (out_f32) SC_LSL(true, 1, 4); else SC_LSL(false, 1, 4); }
+                else { if (out_f32) SC_LSL(true, 2, 3); else SC_LSL(false, 2, 3); }
 #undef SC_LSL
-            SC_CHECK_LAUNCH("sc_gemm_f16");
-            return SC_OK;
-        }
-        static std::atomic<int> unrolled{-1};                 // SC_SKINNY_GENERIC=1 pins the run-time-loop kernel (A/B runs, bit-identity test)
-        if (unrolled < 0) { const char* e = getenv("SC_SKINNY_GENERIC"); unrolled = (e && e[0] == '1') ? 0 : 1; }
-        if constexpr (EPI == SC_EPI_NONE || EPI == SC_EPI_SWIGLU) if (unrolled && (K == 3584 || K == 18944)) {
-#define SC_LSU(F32, MGV, KWV, BTV) hipLaunchKernelGGL((k_gemm_skinny_u<EPI, F32, MGV, KWV, BTV>), grid, block, 0, s, (const _Float16*)A, lda, (const _Float16*)W, \
-                                                      (const _Float16*)bias, (const _Float16*)R, ldr, C, ldc, M, N)
-            static std::atomic<int> xres{-1};                     // SC_SKINNY_XREG=0: the x-from-L2 kernel for K = 3584 too (A/B runs)
-            if (xres < 0) { const char* e = getenv("SC_SKINNY_XREG"); xres = (e && e[0] == '0') ? 0 : 1; }
-            static int n_cu_x[16] = {};
-            if (n_cu_x[dev] == 0) { int n = 0; n_cu_x[dev] = (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n > 0) ? n : 256; }
-            // activations resident in registers, persistent over strips (k_gemm_skinny_x): where a workgroup gets at least two strips (gate/up,
-            // lm_head); with one strip per workgroup (the 3584-row projections) loading x first only delays the weights: k_gemm_skinny_u
-            if (K == 3584 && xres && N / 16 >= 2 * n_cu_x[dev]) {
-                const int strips = N / 16, gx = sc_launch_cu_count(n_cu_x[dev], s);
-                static std::atomic<int> lx{-1};                   // SC_SKINNY_LX=0: weights as register operands (k_gemm_skinny_x) instead of the LDS ring (k_gemm_skinny_lx)
-                if (lx < 0) { const char* e = getenv("SC_SKINNY_LX"); lx = (e && e[0] == '0') ? 0 : 1; }
-                if (lx && lda % 8 == 0 && (!R || ldr % 8 == 0) && ((reinterpret_cast<uintptr_t>(A) | reinterpret_cast<uintptr_t>(W) | reinterpret_cast<uintptr_t>(R) | reinterpret_cast<uintptr_t>(bias)) & 15) == 0) {
-                    static std::atomic<bool> lx_attr[16][4];
-#define SC_LLX(F32, MGV, SLOT) do { constexpr int LDSB = 4 * 8 * 4096 + 3 * MGV * 4 * 64 * 4 + 4 * 2048;                                                        \
-                        if (!lx_attr[dev][SLOT]) { (void)hipFuncSetAttribute((const void*)k_gemm_skinny_lx<EPI, F32, MGV>, hipFuncAttributeMaxDynamicSharedMemorySize, LDSB); lx_attr[dev][SLOT] = true; } \
-                        hipLaunchKernelGGL((k_gemm_skinny_lx<EPI, F32, MGV>), dim3((unsigned)gx), block, LDSB, s, (const _Float16*)A, lda, (const _Float16*)W,           \
-                                           (const _Float16*)bias, (const _Float16*)R, ldr, C, ldc, M, N, strips / gx, strips % gx); } while (0)
-                    if (M <= 16) { if (out_f32) SC_LLX(true, 1, 0); else SC_LLX(false, 1, 1); }
-                    else { if (out_f32) SC_LLX(true, 2, 2); else SC_LLX(false, 2, 3); }
-#undef SC_LLX
-                    SC_CHECK_LAUNCH("sc_gemm_f16");
-                    return SC_OK;
-                }
-#define SC_LSX(F32, MGV) hipLaunchKernelGGL((k_gemm_skinny_x<EPI, F32, MGV>), dim3((unsigned)gx), block, 0, s, (const _Float16*)A, lda, (const _Float16*)W, \
-                                            (const _Float16*)bias, (const _Float16*)R, ldr, C, ldc, M, N, strips / gx, strips % gx)
-                if (M <= 16) { if (out_f32) SC_LSX(true, 1); else SC_LSX(false, 1); }
-                else { if (out_f32) SC_LSX(true, 2); else SC_LSX(false, 2); }
-#undef SC_LSX
                 SC_CHECK_LAUNCH("sc_gemm_f16");
                 return SC_OK;
             }
-            // (one strip per workgroup and at most ~one workgroup per CU: the whole K-quarter of a wave in flight at once - 28 weight + 28 MG
-            //  activation fragments per lane)
-            if (K == 3584) { if (M <= 16) { if (out_f32) SC_LSU(true, 1, 28, 28); else SC_LSU(false, 1, 28, 28); }
-                             else { if (out_f32) SC_LSU(true, 2, 28, 7); else SC_LSU(false, 2, 28, 7); } }
-            else { if (M <= 16) { if (out_f32) SC_LSU(true, 1, 148, 8); else SC_LSU(false, 1, 148, 8); }
-                   else { if (out_f32) SC_LSU(true, 2, 148, 8); else SC_LSU(false, 2, 148, 8); } }
-#undef SC_LSU
-            SC_CHECK_LAUNCH("sc_gemm_f16");
-            return SC_OK;
+            // K = 3584 (Qwen2-7B hidden width) with at least two strips per CU (gate/up, lm_head): activations resident in registers for the
+            // workgroup's lifetime, persistent over strips, weights through the LDS ring (k_gemm_skinny_lx)
+            if (K == 3584) {
+#define SC_LLX(F32, MGV) do { constexpr int LDSB = 4 * 8 * 4096 + 3 * MGV * 4 * 64 * 4 + 4 * 2048;                                                      \
+                    sc_set_max_lds<k_gemm_skinny_lx<EPI, F32, MGV>>(LDSB);                                                                                  \
+                    hipLaunchKernelGGL((k_gemm_skinny_lx<EPI, F32, MGV>), dim3((unsigned)cus), block, LDSB, s, (const _Float16*)A, lda, (const _Float16*)W, \
+                                       (const _Float16*)bias, (const _Float16*)R, ldr, C, ldc, M, N, strips / cus, strips % cus); } while (0)
+                if (M <= 16) { if (out_f32) SC_LLX(true, 1); else SC_LLX(false, 1); }
+                else { if (out_f32) SC_LLX(true, 2); else SC_LLX(false, 2); }
+#undef SC_LLX
+                SC_CHECK_LAUNCH("sc_gemm_f16");
+                return SC_OK;
+            }
         }
+        const dim3 grid((unsigned)(N / 16));
 #define SC_LSK(F32, MGV) hipLaunchKernelGGL((k_gemm_skinny<EPI, F32, MGV>), grid, block, 0, s, (const _Float16*)A, lda, (const _Float16*)W, \
                                               (const _Float16*)bias, (const _Float16*)R, ldr, C, ldc, M, N, K)
         if (M <= 16) { if (out_f32) SC_LSK(true, 1); else SC_LSK(false, 1); }
@@ -1636,75 +1355,25 @@ int launch_gemm(const void* A, int lda, const void* W, const void* bias, const v
         SC_CHECK_LAUNCH("sc_gemm_f16");
         return SC_OK;
     }
-    const bool big = force == 256 || force == 2561 || (force != 128 && M >= 1024);
     const bool wide_ok = out_f32 || (ldc % 8 == 0 && (reinterpret_cast<uintptr_t>(C) & 15) == 0);      // 16-byte epilogue stores
-    if (big && wide_ok && N % BN2 == 0 && K % BK2 == 0) {
-        // 256x256 tiles; the 128x256 / two-workgroups-per-CU variant is kept for A/B runs (SC_GEMM_KERNEL=2561)
-        static std::atomic<int> gmw{-1};                      // raster group for wide N (SC_GEMM_GMW overrides; A/B in profiles/)
-        if (gmw < 0) { const char* e = getenv("SC_GEMM_GMW"); gmw = e ? atoi(e) : 4; }
-        const int gm_sel = (N / BN2) > 16 ? gmw.load() : SC_GEMM_GM;
-        const bool half = force == 2561;        // measured: the 256x256 tile wins at every K once the store tail is widened (K-sweep in profiles)
-        const int bm = half ? 128 : 256;
-        const int tM = (M + bm - 1) / bm, tN = N / BN2;
-        const dim3 grid2((unsigned)(tM * tN)), block2(half ? 256 : 512);
-        const size_t lds2 = half ? 3 * (128 * BK2 * 2 + HALF2) : SC_GEMM_NS * STAGE2;
-        const void* fn = half ? (out_f32 ? (const void*)k_gemm256<EPI, true, 1> : (const void*)k_gemm256<EPI, false, 1>)
-                              : (out_f32 ? (const void*)k_gemm256<EPI, true, 2> : (const void*)k_gemm256<EPI, false, 2>);
-        static std::atomic<bool> attr_done[16][16];
-        const int ai = EPI * 4 + (out_f32 ? 2 : 0) + (half ? 1 : 0);
-        if (!attr_done[dev][ai]) { (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2); attr_done[dev][ai] = true; }
-        // persistent walk (one workgroup per CU) when a workgroup gets more than one tile; needs an even number of K-steps (the
-        // fragment register sets ping-pong in pairs) and at least DIST + 1 of them.  SC_GEMM_PERSIST=0 switches it off (A/B runs).
-        static std::atomic<int> persist{-1}, n_cu_dev[16];
-        if (persist < 0) { const char* e = getenv("SC_GEMM_PERSIST"); persist = e ? atoi(e) : 1; }
-        if (n_cu_dev[dev] == 0) {
-            int cur = 0, n = 0;
-            if (hipGetDevice(&cur) == hipSuccess && hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, cur) == hipSuccess) n_cu_dev[dev] = n;
-            if (n_cu_dev[dev] <= 0) n_cu_dev[dev] = 256;
-        }
-        const int n_cu = sc_launch_cu_count(n_cu_dev[dev], s);          // (a CU-masked stream gets a persistent grid of its own size)
-        const int nt_all = tM * tN, nk2 = K / BK2;
-        // (measured, profiles/r01_run99: +2..4 % at K = 1024, -1..3.5 % at K >= 3584 where the per-tile epilogue is a small share)
-        static std::atomic<int> fat{-1};
-        if (fat < 0) { const char* e = getenv("SC_GEMM_FAT"); fat = e ? atoi(e) : 1; }
-        if (fat && !half && !out_f32 && a_grp == 0 && K % 128 == 0 && (size_t)lda * 512 < (1ull << 31) && lda % 8 == 0 &&
-            (reinterpret_cast<uintptr_t>(A) & 15) == 0 && (reinterpret_cast<uintptr_t>(W) & 15) == 0 &&          // 16-byte DMA granules
-            (!bias || (reinterpret_cast<uintptr_t>(bias) & 15) == 0) && (!R || (ldr % 8 == 0 && (reinterpret_cast<uintptr_t>(R) & 15) == 0))) {       // (16-byte residual rows: loads along rows + the DMA of the first row tile)
-            // persistent walk (one workgroup per CU) once there are more tiles than CUs: the next tile's first iterations are
-            // fetched under the epilogue of the current one
-            const bool fp = persist && fat != 2 && nt_all > n_cu;
+    if (M >= 1024 && wide_ok && N % BN2 == 0 && K % BK2 == 0) {
+        // fp16 output: the hand-scheduled k_gemm_fat (16-byte DMA granules; 16-byte residual rows: loads along rows + the DMA of the first row tile)
+        if (!out_f32 && a_grp == 0 && K % 128 == 0 && (size_t)lda * 512 < (1ull << 31) && lda % 8 == 0 &&
+            (reinterpret_cast<uintptr_t>(A) & 15) == 0 && (reinterpret_cast<uintptr_t>(W) & 15) == 0 &&
+            (!bias || (reinterpret_cast<uintptr_t>(bias) & 15) == 0) && (!R || (ldr % 8 == 0 && (reinterpret_cast<uintptr_t>(R) & 15) == 0))) {
             constexpr bool CAN_R = EPI == SC_EPI_NONE || EPI == SC_EPI_QUICK_GELU || EPI == SC_EPI_GELU_ERF;
             SC_REQUIRE(CAN_R || !R, "sc_gemm_f16: this epilogue takes no residual");
-            static std::atomic<bool> fattr[16][8][2][2];
-            const bool res = CAN_R && R != nullptr;
-            const void* kfn = res ? (fp ? (const void*)k_gemm_fat<EPI, true, CAN_R> : (const void*)k_gemm_fat<EPI, false, CAN_R>)
-                                  : (fp ? (const void*)k_gemm_fat<EPI, true, false> : (const void*)k_gemm_fat<EPI, false, false>);
-            if (!fattr[dev][EPI][fp][res]) {
-                (void)hipFuncSetAttribute(kfn, hipFuncAttributeMaxDynamicSharedMemorySize, 163840);
-                fattr[dev][EPI][fp][res] = true;
-            }
-#define SC_LFAT(P, RS, GRID)                                                                                                              \
-            hipLaunchKernelGGL((k_gemm_fat<EPI, P, RS>), GRID, dim3(256), 163840, s, (const _Float16*)A, lda, (const _Float16*)W, (const _Float16*)bias, \
-                               (const _Float16*)R, ldr, C, ldc, M, N, K, tN, gm_sel, nt_all, (const float*)nullptr, 0, 0, 1.0f)
-            if (res) { if (fp) SC_LFAT(true, CAN_R, dim3(n_cu)); else SC_LFAT(false, CAN_R, grid2); }
-            else { if (fp) SC_LFAT(true, false, dim3(n_cu)); else SC_LFAT(false, false, grid2); }
-#undef SC_LFAT
-            SC_CHECK_LAUNCH("sc_gemm_f16");
-            return SC_OK;
+            if (CAN_R && R) return launch_fat<EPI, CAN_R>(A, lda, W, bias, R, ldr, C, ldc, M, N, K, nullptr, 0, 0, 1.0f, s, "sc_gemm_f16");
+            return launch_fat<EPI, false>(A, lda, W, bias, R, ldr, C, ldc, M, N, K, nullptr, 0, 0, 1.0f, s, "sc_gemm_f16");
         }
-        const bool pers = persist && !half && !out_f32 && nt_all > n_cu && (nk2 % 2 == 0) && nk2 >= 4 && nk2 <= 64 && a_grp == 0 &&
-                          (size_t)M * (size_t)lda * 2 < (1ull << 31) && (size_t)N * (size_t)K * 2 < (1ull << 31);
-#define SC_L256(F32, WRV)                                                                                                                 \
-        hipLaunchKernelGGL((k_gemm256<EPI, F32, WRV>), grid2, block2, lds2, s, (const _Float16*)A, lda, (const _Float16*)W, (const _Float16*)bias, \
-                           (const _Float16*)R, ldr, C, ldc, M, N, K, tN, a_grp, a_grp_stride, a_grp_off, gm_sel, nt_all)
-        if (pers) {
-            static std::atomic<bool> pattr[16][8];
-            if (!pattr[dev][EPI]) { (void)hipFuncSetAttribute((const void*)k_gemm256<EPI, false, 2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2); pattr[dev][EPI] = true; }
-            hipLaunchKernelGGL((k_gemm256<EPI, false, 2, true>), dim3((unsigned)n_cu), block2, lds2, s, (const _Float16*)A, lda, (const _Float16*)W,
-                               (const _Float16*)bias, (const _Float16*)R, ldr, C, ldc, M, N, K, tN, a_grp, a_grp_stride, a_grp_off, gm_sel, nt_all);
-        }
-        else if (half) { if (out_f32) SC_L256(true, 1); else SC_L256(false, 1); }
-        else { if (out_f32) SC_L256(true, 2); else SC_L256(false, 2); }
+        // the rest (fp32 output, the row-mapped A operand, K % 128 != 0, 8-byte aligned bias / residual): k_gemm256, one tile per workgroup
+        const int tN = N / BN2;
+        const dim3 grid2((unsigned)(((M + BM2 - 1) / BM2) * tN)), block2(512);
+        constexpr int LDS2 = SC_GEMM_NS * STAGE2;
+#define SC_L256(F32) do { sc_set_max_lds<k_gemm256<EPI, F32>>(LDS2);                                                                                \
+            hipLaunchKernelGGL((k_gemm256<EPI, F32>), grid2, block2, LDS2, s, (const _Float16*)A, lda, (const _Float16*)W, (const _Float16*)bias,  \
+                               (const _Float16*)R, ldr, C, ldc, M, N, K, tN, a_grp, a_grp_stride, a_grp_off, raster_group(tN)); } while (0)
+        if (out_f32) SC_L256(true); else SC_L256(false);
 #undef SC_L256
         SC_CHECK_LAUNCH("sc_gemm_f16");
         return SC_OK;
@@ -1724,36 +1393,6 @@ int launch_gemm(const void* A, int lda, const void* W, const void* bias, const v
 
 }  // namespace
 
-namespace {
-template <int EPI>
-int launch_headed(const void* A, int lda, const void* W, const void* bias, void* C, int ldc, int M, int N, int K, const float* tab, int pos0, int lead_cols,
-                  float col_scale, hipStream_t s) {
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    dev &= 15;
-    static std::atomic<int> n_cu_dev[16];
-    if (n_cu_dev[dev] == 0) {
-        int cur = 0, n = 0;
-        if (hipGetDevice(&cur) == hipSuccess && hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, cur) == hipSuccess) n_cu_dev[dev] = n;
-        if (n_cu_dev[dev] <= 0) n_cu_dev[dev] = 256;
-    }
-    const int n_cu = sc_launch_cu_count(n_cu_dev[dev], s), tM = (M + BM2 - 1) / BM2, tN = N / BN2, nt_all = tM * tN;
-    const bool fp = nt_all > n_cu;                                   // persistent walk once there are more tiles than CUs (as in launch_gemm)
-    const int gm_sel = tN > 16 ? 4 : SC_GEMM_GM;
-    static std::atomic<bool> attr[16][2];
-    if (!attr[dev][fp]) {
-        (void)hipFuncSetAttribute(fp ? (const void*)k_gemm_fat<EPI, true> : (const void*)k_gemm_fat<EPI, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 163840);
-        attr[dev][fp] = true;
-    }
-    if (fp) hipLaunchKernelGGL((k_gemm_fat<EPI, true>), dim3(n_cu), dim3(256), 163840, s, (const _Float16*)A, lda, (const _Float16*)W, (const _Float16*)bias,
-                               (const _Float16*)nullptr, 0, C, ldc, M, N, K, tN, gm_sel, nt_all, tab, pos0, lead_cols, col_scale);
-    else hipLaunchKernelGGL((k_gemm_fat<EPI, false>), dim3((unsigned)nt_all), dim3(256), 163840, s, (const _Float16*)A, lda, (const _Float16*)W, (const _Float16*)bias,
-                            (const _Float16*)nullptr, 0, C, ldc, M, N, K, tN, gm_sel, nt_all, tab, pos0, lead_cols, col_scale);
-    SC_CHECK_LAUNCH("sc_gemm_headed_f16");
-    return SC_OK;
-}
-}  // namespace
-
 // C = headed_epilogue(A W^T + bias): the GEMM whose epilogue knows that the output columns are heads of width 128 (hand-scheduled kernel only)
 extern "C" int sc_gemm_headed_f16(const void* A, int lda, const void* W, const void* bias, void* C, int ldc, int M, int N, int K, int mode,
                                   const float* rope_tab, int rope_tab_rows, int pos0, int lead_cols, float col_scale, sc_stream_t stream) {
@@ -1767,9 +1406,10 @@ extern "C" int sc_gemm_headed_f16(const void* A, int lda, const void* W, const v
           ((reinterpret_cast<uintptr_t>(A) | reinterpret_cast<uintptr_t>(W) | reinterpret_cast<uintptr_t>(C) | reinterpret_cast<uintptr_t>(bias)) & 15) == 0))
         return sc_fail(SC_ERR_UNSUPPORTED, "sc_gemm_headed_f16: needs N %% 256 == 0, K %% 128 == 0, lda %% 8 == 0, ldc %% 8 == 0 and 16-byte aligned A / W / C / bias");
     hipStream_t s = (hipStream_t)stream;
-    if (mode == SC_EPI_ROPE && lead_cols >= N) return launch_headed<SC_EPI_ROPE_ALL>(A, lda, W, bias, C, ldc, M, N, K, rope_tab, pos0, N, 1.0f, s);
-    if (mode == SC_EPI_ROPE) return launch_headed<SC_EPI_ROPE>(A, lda, W, bias, C, ldc, M, N, K, rope_tab, pos0, lead_cols, 1.0f, s);
-    return launch_headed<SC_EPI_COLSCALE>(A, lda, W, bias, C, ldc, M, N, K, nullptr, 0, lead_cols, col_scale, s);
+    const char* api = "sc_gemm_headed_f16";
+    if (mode == SC_EPI_ROPE && lead_cols >= N) return launch_fat<SC_EPI_ROPE_ALL, false>(A, lda, W, bias, nullptr, 0, C, ldc, M, N, K, rope_tab, pos0, N, 1.0f, s, api);
+    if (mode == SC_EPI_ROPE) return launch_fat<SC_EPI_ROPE, false>(A, lda, W, bias, nullptr, 0, C, ldc, M, N, K, rope_tab, pos0, lead_cols, 1.0f, s, api);
+    return launch_fat<SC_EPI_COLSCALE, false>(A, lda, W, bias, nullptr, 0, C, ldc, M, N, K, nullptr, 0, lead_cols, col_scale, s, api);
 }
 
 extern "C" int sc_gemm_f16(const void* A, int lda, const void* W, const void* bias, const void* residual, int ldr, void* C, int ldc,

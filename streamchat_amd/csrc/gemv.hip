@@ -152,16 +152,13 @@ const _Float16* __restrict__ W, const _Float16* __restrict__ x, const _Float16* 
 // pure launch + latency inside the captured decode graph):
 //   [q | k | v] = W . rmsnorm(x) + b;  rotate-half RoPE of q and k at position p = pos[0];  q -> q_out,  k | v -> cache row p.
 // One wave owns the two rows (h, j) and (h, j + Dh/2) of a head, i.e. one RoPE rotation pair, so the rotation happens in the
-// epilogue of lane 0 with the arithmetic of k_rope_qk_row (llm_ops.hip: fp32 trig, cos / sin and every product rounded to fp16 like
-// HF's apply_rotary_pos_emb) on the fp16-rounded projections: bit-identical to the three-launch path.  V rows ride along unrotated.
-// TAB: the rotation uses the fp32 cos / sin tables of sc_rope_table_f32 (tab_q carries the softmax scale * log2 e: the query leaves
+// epilogue of lane 0.  It uses the fp32 cos / sin tables of sc_rope_table_f32 (tab_q carries the softmax scale * log2 e: the query leaves
 // pre-scaled for sc_attention_f16's SC_ATTN_Q_PRESCALED mode) on the fp32 accumulators + bias, rounded to fp16 ONCE - the numerics of
-// the prefill GEMM's rotary epilogue (gemm.hip) and of k_rope_f32in.
-template <bool TAB>
+// the prefill GEMM's rotary epilogue (gemm.hip) and of k_rope_f32in.  V rows ride along unrotated.
 __global__ __launch_bounds__(512) void k_decode_qkv(const _Float16* __restrict__ Wq, const _Float16* __restrict__ Wkv, const _Float16* __restrict__ bq,
                                                     const _Float16* __restrict__ bkv, const _Float16* __restrict__ x, const _Float16* __restrict__ gamma,
                                                     float eps, _Float16* __restrict__ q_out, _Float16* __restrict__ cache, int ld,
-                                                    const int* __restrict__ pos, int Hq, int Hkv, int Dh, int K, float log2_theta,
+                                                    const int* __restrict__ pos, int Hq, int Hkv, int Dh, int K,
                                                     const float* __restrict__ tab_q, const float* __restrict__ tab_k, int tab_rows) {
     const int lane = threadIdx.x & 63;
     const int half = Dh >> 1;
@@ -180,7 +177,7 @@ __global__ __launch_bounds__(512) void k_decode_qkv(const _Float16* __restrict__
     const int row = pos[0];
     const float bias0 = (live && b0) ? (float)b0[0] : 0.f, bias1 = (live && b0) ? (float)b0[half] : 0.f;
     float tcs = 1.f, tsn = 0.f;
-    if (TAB && live && kind != 2) {
+    if (live && kind != 2) {
         const int trow = row < 0 ? 0 : (row >= tab_rows ? tab_rows - 1 : row);      // the position lives in device memory: clamp to the table, never read past it
         const float* t = (kind == 0 ? tab_q : tab_k) + (size_t)trow * (size_t)Dh;
         tcs = t[j]; tsn = t[half + j];
@@ -235,25 +232,14 @@ __global__ __launch_bounds__(512) void k_decode_qkv(const _Float16* __restrict__
         const _Float16 a = (_Float16)(acc0 + bias0), b = (_Float16)(acc1 + bias1);
         _Float16* dst = kind == 0 ? q_out + h * Dh + j : cache + (size_t)row * (size_t)ld + (kind == 1 ? 0 : Hkv * Dh) + h * Dh + j;
         if (kind == 2) { dst[0] = a; dst[half] = b; return; }
-        if (TAB) {
-            const float a32 = acc0 + bias0, b32 = acc1 + bias1, cs = tcs, sn = tsn;
-            // fp32 fma FIRST, then the rounding to fp16 - as k_rope_f32in and the GEMM epilogue do it: left alone, hipcc fuses the two into
-            // v_fma_mixlo_f16 (ONE rounding of the exact product-sum), which differs from fma -> cvt in the last fp16 bit on ties and made the
-            // captured decode graph and the eager step disagree by one ulp in a K row every few tokens
-            float ra = __builtin_fmaf(-b32, sn, a32 * cs), rb = __builtin_fmaf(a32, sn, b32 * cs);
-            asm volatile("" : "+v"(ra), "+v"(rb));
-            dst[0] = (_Float16)ra;
-            dst[half] = (_Float16)rb;
-            return;
-        }
-        const float inv_freq = exp2f(-log2_theta * (float)(2 * j) / (float)Dh);
-        float sn, cs;
-        sincosf((float)row * inv_freq, &sn, &cs);
-        const _Float16 c16 = (_Float16)cs, s16 = (_Float16)sn;
-        const _Float16 t1 = (_Float16)((float)a * (float)c16), t2 = (_Float16)((float)b * (float)s16);
-        const _Float16 t3 = (_Float16)((float)b * (float)c16), t4 = (_Float16)((float)a * (float)s16);
-        dst[0] = (_Float16)((float)t1 - (float)t2);
-        dst[half] = (_Float16)((float)t3 + (float)t4);
+        const float a32 = acc0 + bias0, b32 = acc1 + bias1, cs = tcs, sn = tsn;
+        // fp32 fma FIRST, then the rounding to fp16 - as k_rope_f32in and the GEMM epilogue do it: left alone, hipcc fuses the two into
+        // v_fma_mixlo_f16 (ONE rounding of the exact product-sum), which differs from fma -> cvt in the last fp16 bit on ties and made the
+        // captured decode graph and the eager step disagree by one ulp in a K row every few tokens
+        float ra = __builtin_fmaf(-b32, sn, a32 * cs), rb = __builtin_fmaf(a32, sn, b32 * cs);
+        asm volatile("" : "+v"(ra), "+v"(rb));
+        dst[0] = (_Float16)ra;
+        dst[half] = (_Float16)rb;
     }
 }
 
@@ -420,7 +406,7 @@ __global__ __launch_bounds__(64 * WPB) void k_gemv_u(const _Float16* __restrict_
     }
 }
 
-// k_decode_qkv<true> for K = NS * 512 and four waves per workgroup (see k_gemv_u); queue: [bias pair] [x, gamma] [both weight rows,
+// k_decode_qkv for K = NS * 512 and four waves per workgroup (see k_gemv_u); queue: [bias pair] [x, gamma] [both weight rows,
 // all NS slices] [rotary table pair - its address needs pos[0], a scalar load: behind the weights, the stream does not wait for it]
 template <int NS>
 __global__ __launch_bounds__(256) void k_decode_qkv_u(const _Float16* __restrict__ Wq, const _Float16* __restrict__ Wkv, const _Float16* __restrict__ bq,
@@ -505,23 +491,6 @@ bool use_specialised() {
 
 }  // namespace
 
-extern "C" int sc_decode_qkv_f16(const void* Wq, const void* Wkv, const void* bq, const void* bkv, const void* x, const void* rms_gamma, float rms_eps,
-                                 void* q_out, void* cache, int cache_ld, const int32_t* pos, int q_heads, int kv_heads, int Dh, int K, float theta,
-                                 sc_stream_t stream) {
-    SC_REQUIRE(Wq && Wkv && x && q_out && cache && pos, "sc_decode_qkv_f16: null pointer argument");
-    SC_REQUIRE(q_heads > 0 && kv_heads > 0 && Dh > 0 && Dh % 2 == 0 && K > 0 && K % 8 == 0, "sc_decode_qkv_f16: bad sizes");
-    SC_REQUIRE(cache_ld >= 2 * kv_heads * Dh, "sc_decode_qkv_f16: cache row stride too small for K | V");
-    SC_REQUIRE(((reinterpret_cast<uintptr_t>(Wq) | reinterpret_cast<uintptr_t>(Wkv) | reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(rms_gamma)) & 15) == 0,
-               "sc_decode_qkv_f16: weights, x and gamma must be 16-byte aligned");
-    const int ntask = (q_heads + 2 * kv_heads) * (Dh / 2);
-    const int wpb = pick_wpb(0);
-    hipLaunchKernelGGL(k_decode_qkv<false>, dim3((unsigned)((ntask + wpb - 1) / wpb)), dim3(64 * wpb), rms_gamma ? (size_t)K * 2 + 16 : 0, (hipStream_t)stream, (const _Float16*)Wq, (const _Float16*)Wkv,
-                       (const _Float16*)bq, (const _Float16*)bkv, (const _Float16*)x, (const _Float16*)rms_gamma, rms_eps, (_Float16*)q_out, (_Float16*)cache,
-                       cache_ld, pos, q_heads, kv_heads, Dh, K, log2f(theta), (const float*)nullptr, (const float*)nullptr, 0);
-    SC_CHECK_LAUNCH("sc_decode_qkv_f16");
-    return SC_OK;
-}
-
 extern "C" int sc_decode_qkv_tab_f16(const void* Wq, const void* Wkv, const void* bq, const void* bkv, const void* x, const void* rms_gamma, float rms_eps,
                                      void* q_out, void* cache, int cache_ld, const int32_t* pos, int q_heads, int kv_heads, int Dh, int K,
                                      const float* tab_q, const float* tab_k, int tab_rows, sc_stream_t stream) {
@@ -539,9 +508,9 @@ extern "C" int sc_decode_qkv_tab_f16(const void* Wq, const void* Wkv, const void
         return SC_OK;
     }
     const int wpb = pick_wpb(0);
-    hipLaunchKernelGGL(k_decode_qkv<true>, dim3((unsigned)((ntask + wpb - 1) / wpb)), dim3(64 * wpb), rms_gamma ? (size_t)K * 2 + 16 : 0, (hipStream_t)stream, (const _Float16*)Wq, (const _Float16*)Wkv,
+    hipLaunchKernelGGL(k_decode_qkv, dim3((unsigned)((ntask + wpb - 1) / wpb)), dim3(64 * wpb), rms_gamma ? (size_t)K * 2 + 16 : 0, (hipStream_t)stream, (const _Float16*)Wq, (const _Float16*)Wkv,
                        (const _Float16*)bq, (const _Float16*)bkv, (const _Float16*)x, (const _Float16*)rms_gamma, rms_eps, (_Float16*)q_out, (_Float16*)cache,
-                       cache_ld, pos, q_heads, kv_heads, Dh, K, 0.f, tab_q, tab_k, tab_rows);
+                       cache_ld, pos, q_heads, kv_heads, Dh, K, tab_q, tab_k, tab_rows);
     SC_CHECK_LAUNCH("sc_decode_qkv_tab_f16");
     return SC_OK;
 }

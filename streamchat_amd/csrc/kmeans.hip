@@ -29,7 +29,6 @@
 // Compiled with -ffp-contract=off: every fma below is explicit.
 #include "sc_common.h"
 #include <stdlib.h>
-#include <mutex>
 #include <type_traits>
 
 namespace {
@@ -1040,9 +1039,8 @@ void launch_update(bool vec, const void* X, float* Ca, float* Cb, const KmWs& w,
 // ---- the one-read pass: which shapes take it, and its launch ----------------------------------
 // SC_KM_FUSED=0 forces the two-pass kernels everywhere (same bits: tests/test_gpu_kmeans_fused.py compares the two paths).
 bool km2_enabled() {
-    static int on = -1;
-    if (on < 0) { const char* e = getenv("SC_KM_FUSED"); on = (e && e[0] == '0') ? 0 : 1; }
-    return on != 0;
+    static const bool on = [] { const char* e = getenv("SC_KM_FUSED"); return !(e && e[0] == '0'); }();
+    return on;
 }
 // rows-per-wave bucket: the slab holds RGW * 64 rows and must take the T rows sorted by cluster with every cluster padded to whole 8-row groups.
 // With few rows a slice is too little work per workgroup step (two barriers, one DMA round trip), and the K = 8 instantiation carries 64
@@ -1066,8 +1064,7 @@ template <int K, int RGW, int MODE>
 void km2_launch_inst(const void* X, float* Ca, float* Cb, const KmWs& w, const float* wts, const int32_t* reseed_idx, int n_reseed, int T, int64_t D,
                      hipStream_t s) {
     constexpr size_t lds = km2_lds_bytes(K, RGW);
-    static std::once_flag once;
-    std::call_once(once, [] { (void)hipFuncSetAttribute((const void*)km2_pass<K, RGW, MODE>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); });
+    sc_set_max_lds<km2_pass<K, RGW, MODE>>((int)lds);
     const int64_t ng = (D + GW - 1) / GW;
     hipLaunchKernelGGL((km2_pass<K, RGW, MODE>), dim3((unsigned)ng), dim3(KM2_NW * 64), lds, s, (const _Float16*)X, Ca, Cb, w.st, wts,
                        w.order, w.start, w.W, w.empty_rank, reseed_idx, n_reseed, w.dgpart, w.gpart, T, D);

@@ -5,6 +5,8 @@
 #include <stdint.h>
 #include <stdio.h>
 
+#include <atomic>
+
 #include "../../include/streamchat_hip.h"
 
 #define SC_WAVE 64
@@ -28,7 +30,25 @@ static inline int sc_fail(int code, const char* fmt, ...) {
         if (e_ != hipSuccess) return sc_fail(SC_ERR_LAUNCH, "%s: %s", name, hipGetErrorString(e_)); \
     } while (0)
 
-int sc_launch_cu_count(int device_cus, hipStream_t stream);      // CUs a persistent launch on `stream` may count on (core.hip)
+// CU counts (core.hip).  sc_device_cu_count: the current device's, cached per device (256 if it cannot be queried); sc_launch_cu_count: what a
+// persistent launch on `stream` may count on (a CU-masked stream's own size)
+int sc_device_cu_count();
+int sc_launch_cu_count(hipStream_t stream);
+
+// Raise KERNEL's dynamic-LDS limit to `bytes` on the current device.  The attribute is per device (a process that drives several GPUs - the
+// reference puts its two model replicas on cuda:0 / cuda:1 - raises it on each of them), so the flag is per device and per kernel instantiation;
+// after the first launch on a device this is one atomic load.
+template <auto KERNEL>
+inline void sc_set_max_lds(int bytes) {
+    static std::atomic<bool> done[16];
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    std::atomic<bool>& d = done[dev & 15];
+    if (!d.load(std::memory_order_acquire)) {
+        (void)hipFuncSetAttribute((const void*)KERNEL, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+        d.store(true, std::memory_order_release);
+    }
+}
 
 static inline size_t sc_align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 

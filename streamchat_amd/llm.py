@@ -266,7 +266,7 @@ def _decode_one(self, embeds):
     tq, tk = self.rope_tabs(S)
     for l, L in enumerate(self.L):
         # RMSNorm fused into the projections; fp32 sums -> RoPE with the fp32 tables -> ONE rounding (q pre-scaled): the arithmetic of
-        # k_decode_qkv<true> (the captured graph's single launch) in three launches
+        # k_decode_qkv (the captured graph's single launch) in three launches
         q32 = ops.gemv(L["wq"], h, L["bq"], out_f32=True, rms_gamma=L["ln1"], rms_eps=c.eps).view(1, dq)
         kv32 = ops.gemv(L["wkv"], h, L["bkv"], out_f32=True, rms_gamma=L["ln1"], rms_eps=c.eps).view(1, 2 * dkv)
         q = ops.rope_f32in(q32, tq, c.heads, Dh, torch.empty((1, dq), dtype=torch.float16, device=self.device), 0, pos0)

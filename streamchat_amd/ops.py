@@ -720,18 +720,6 @@ def avgpool_tokens(x, r: int):
     return out
 
 
-def rope_(x, heads: int, Dh: int, theta: float, pos0: int = 0, positions=None):
-    """in-place rotate-half RoPE on x [rows, >= heads*Dh] (row-strided view allowed)."""
-    _require_cuda(x)
-    lib = _lib.load()
-    from ctypes import c_void_p
-    pos = None if positions is None else positions.to(device=x.device, dtype=torch.int32).contiguous()
-    with torch.cuda.device(x.device):
-        check(lib.sc_rope_f16(c_void_p(x.data_ptr()), x.stride(0), ptr(pos), pos0, x.shape[0], heads, Dh, c_float(theta),
-                              stream_ptr(x.device)), "sc_rope_f16")
-    return x
-
-
 def gemv(w, x, bias=None, residual=None, epilogue: str = "none", out=None, out_f32: bool = False, out_row=None, rms_gamma=None, rms_eps=1e-6):
     """y[N] = w[N,K] @ x[K] (+ bias) (+ residual): batch-1 decode projection (weights streamed once)."""
     _require_cuda(w, x)
@@ -753,22 +741,11 @@ def gemv(w, x, bias=None, residual=None, epilogue: str = "none", out=None, out_f
     return out
 
 
-def decode_qkv(wq, wkv, bq, bkv, x, rms_gamma, rms_eps: float, q_out, cache, row_index, q_heads: int, kv_heads: int, Dh: int, theta: float):
-    """one launch: q / k / v projections of ONE token (fused RMSNorm), RoPE of q and k at position row_index[0] (device int32),
-    q -> q_out [q_heads*Dh], k | v -> cache[row_index[0]].  Bit-identical to gemv + gemv + rope_qk_row_."""
-    _require_cuda(wq, wkv, x, q_out, cache, row_index)
-    lib = _lib.load()
-    from ctypes import c_void_p
-    with torch.cuda.device(x.device), _timed("k_gemv", 2.0 * (wq.shape[0] + wkv.shape[0]) * wq.shape[1]):
-        check(lib.sc_decode_qkv_f16(ptr(wq), ptr(wkv), ptr(bq), ptr(bkv), ptr(x.reshape(-1)), ptr(rms_gamma), c_float(rms_eps), c_void_p(q_out.data_ptr()),
-                                    c_void_p(cache.data_ptr()), cache.stride(0), ptr(row_index), q_heads, kv_heads, Dh, wq.shape[1], c_float(theta),
-                                    stream_ptr(x.device)), "sc_decode_qkv_f16")
-    return q_out
-
-
 def decode_qkv_tab(wq, wkv, bq, bkv, x, rms_gamma, rms_eps: float, q_out, cache, row_index, q_heads: int, kv_heads: int, Dh: int, tab_q, tab_k):
-    """decode_qkv with the one-rounding rotary arithmetic of the prefill GEMM epilogue: RoPE of the fp32 sums with the fp32 tables (tab_q carries
-    the softmax scale * log2 e: q_out is pre-scaled), rounded once.  Bit-identical to gemv(out_f32) + rope_f32in."""
+    """one launch: q / k / v projections of ONE token (fused RMSNorm), RoPE of q and k at position row_index[0] (device int32) with the
+    one-rounding rotary arithmetic of the prefill GEMM epilogue: the fp32 sums rotated with the fp32 tables (tab_q carries the softmax
+    scale * log2 e: q_out is pre-scaled), rounded once; q -> q_out [q_heads*Dh], k | v -> cache[row_index[0]].  Bit-identical to
+    gemv(out_f32) + rope_f32in."""
     _require_cuda(wq, wkv, x, q_out, cache, row_index, tab_q, tab_k)
     lib = _lib.load()
     from ctypes import c_void_p
@@ -787,26 +764,3 @@ def decode_advance(nxt, ring, cnt, tok, pos, kv_len, nprev):
         raise StreamChatHipError("decode_advance: dtypes must be int64 (next, ring, index) / int32 (token, pos, kv_len, n_prev)")
     with torch.cuda.device(nxt.device):
         check(_lib.load().sc_decode_advance(ptr(nxt), ptr(ring), ptr(cnt), ptr(tok), ptr(pos), ptr(kv_len), ptr(nprev), stream_ptr(nxt.device)), "sc_decode_advance")
-
-
-def rope_qk_row_(q, q_heads: int, cache, row_index, kv_heads: int, Dh: int, theta: float):
-    """decode step: in-place RoPE of the query row `q` [q_heads*Dh] and of the K part of cache row `row_index` (device int32) - one launch."""
-    _require_cuda(q, cache, row_index)
-    lib = _lib.load()
-    from ctypes import c_void_p
-    with torch.cuda.device(q.device):
-        check(lib.sc_rope_qk_row_f16(c_void_p(q.data_ptr()), q_heads, c_void_p(cache.data_ptr()), cache.stride(0), ptr(row_index), kv_heads, Dh,
-                                     c_float(theta), stream_ptr(q.device)), "sc_rope_qk_row_f16")
-    return q
-
-
-def rope_row_(buf, row_index, heads: int, Dh: int, theta: float):
-    """in-place RoPE on ONE row of `buf` [rows, ld]; the row number (= the token position) is read from the device int32 tensor
-    `row_index` — hipGraph-replayable KV-cache append."""
-    _require_cuda(buf, row_index)
-    lib = _lib.load()
-    from ctypes import c_void_p
-    with torch.cuda.device(buf.device):
-        check(lib.sc_rope_row_f16(c_void_p(buf.data_ptr()), buf.stride(0), ptr(row_index), heads, Dh, c_float(theta), stream_ptr(buf.device)),
-              "sc_rope_row_f16")
-    return buf

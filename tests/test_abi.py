@@ -25,9 +25,9 @@ def test_binding_covers_header(hip_lib):
     assert sorted(_lib.SIGNATURES) == declared_symbols()
 
 
-def test_abi_version_and_error_text(hip_lib):
-    assert hip_lib.sc_abi_version() == 8
-    assert b"abi=8" in hip_lib.sc_build_info() and b"attention=" in hip_lib.sc_build_info()
+def test_abi9_version_and_error_text(hip_lib):
+    assert hip_lib.sc_abi_version() == 9
+    assert b"abi=9" in hip_lib.sc_build_info() and b"attention=" in hip_lib.sc_build_info()
     # argument validation happens before any device work, so it is callable without a GPU
     rc = hip_lib.sc_kmeans_fit(None, 0, 1, 8, 1, None, None, None, 0, 1, 1e-4, None, None, None, None, None, 0, None)
     assert rc == -1
@@ -35,15 +35,18 @@ def test_abi_version_and_error_text(hip_lib):
     assert hip_lib.sc_kmeans_workspace_bytes(400, 576 * 3584, 5) > 0
 
 
-def test_abi_version_matches_header_and_changelog_names_every_symbol_added_since_v2(hip_lib):
+def test_abi_version_matches_header_changelog_and_removed_symbols_are_gone(hip_lib):
     src = open(os.path.join(ROOT, "include", "streamchat_hip.h")).read()
     ver = int(re.search(r"#define\s+SC_ABI_VERSION\s+(\d+)", src).group(1))
     assert hip_lib.sc_abi_version() == ver
     log = src[src.index("ABI changelog"):src.index("#define SC_ABI_VERSION")]
-    for name in ("sc_kmeans_update", "sc_decode_qkv_f16", "sc_pick_token_f32", "sc_sample_token_f32", "sc_attention_variant"):
+    for name in ("sc_kmeans_update", "sc_pick_token_f32", "sc_sample_token_f32", "sc_attention_variant"):
         assert name in log and name in declared_symbols()
     # ABI 7: the process-wide CU budget is gone from the header, the library and the binding; the INTEGRATION.md stub pins the SAME literal
     assert "sc_set_cu_budget" not in declared_symbols() and not hasattr(hip_lib, "sc_set_cu_budget")
+    # ABI 9: the rotary kernels that computed their angles from `theta` are gone (the fp32 table and its consumers replaced them)
+    for name in ("sc_rope_f16", "sc_rope_row_f16", "sc_rope_qk_row_f16", "sc_decode_qkv_f16"):
+        assert name not in declared_symbols() and not hasattr(hip_lib, name)
     integ = open(os.path.join(ROOT, "INTEGRATION.md")).read()
     assert int(re.search(r"^SC_ABI_VERSION\s*=\s*(\d+)", integ, re.M).group(1)) == ver
     assert "sc_abi_version() == SC_ABI_VERSION" in integ

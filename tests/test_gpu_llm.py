@@ -74,17 +74,8 @@ def test_splice_matches_reference():
         assert torch.equal(out2, ref), k
 
 
-def test_rope_and_swiglu_kernels_vs_torch():
+def test_swiglu_gemm_epilogue_vs_torch():
     g = torch.Generator(device="cuda").manual_seed(0)
-    x = torch.randn(50, 4 * 128, device="cuda", generator=g).half()
-    y = ops.rope_(x.clone(), 4, 128, 1e6, pos0=1000)
-    pos = torch.arange(1000, 1050, device="cuda", dtype=torch.float32)
-    inv = 1.0 / (1e6 ** (torch.arange(0, 128, 2, device="cuda", dtype=torch.float32) / 128))
-    fr = torch.outer(pos, inv)
-    cos, sin = torch.cat([fr, fr], -1).cos()[:, None], torch.cat([fr, fr], -1).sin()[:, None]
-    xf = x.float().view(50, 4, 128)
-    ref = xf * cos + torch.cat([-xf[..., 64:], xf[..., :64]], -1) * sin
-    torch.testing.assert_close(y.float().view(50, 4, 128), ref, rtol=4e-3, atol=4e-3)
     a = torch.randn(70, 256, device="cuda", generator=g).half()
     wg, wu = (torch.randn(384, 256, device="cuda", generator=g) / 16).half(), (torch.randn(384, 256, device="cuda", generator=g) / 16).half()
     wgu = torch.cat([wg.view(192, 2, 256), wu.view(192, 2, 256)], 1).reshape(768, 256).contiguous()
@@ -191,21 +182,6 @@ def test_batch_decoder_leaves_the_models_prompt_state_untouched():
     dg.start(first)
     dg.run(1)
     assert torch.equal(dg.logits.view(torch.int32), eager.view(torch.int32))
-
-
-def test_rope_qk_row_equals_separate_ropes():
-    """the fused decode RoPE (query row + K part of the cache row, one launch) is bit-identical to the two separate kernels"""
-    g = torch.Generator(device="cuda").manual_seed(3)
-    q = torch.randn(1, 28 * 128, device="cuda", generator=g).half()
-    cache = torch.randn(300, 2 * 4 * 128, device="cuda", generator=g).half()
-    pos = torch.tensor([217], dtype=torch.int32, device="cuda")
-    q1, c1 = q.clone(), cache.clone()
-    ops.rope_(q1, 28, 128, 1e6, positions=pos)
-    ops.rope_row_(c1, pos, 4, 128, 1e6)
-    q2, c2 = q.clone(), cache.clone()
-    ops.rope_qk_row_(q2, 28, c2, pos, 4, 128, 1e6)
-    assert torch.equal(q1, q2) and torch.equal(c1, c2)
-    assert torch.equal(c2[:217], cache[:217]) and torch.equal(c2[218:], cache[218:]) and torch.equal(c2[217, 512:], cache[217, 512:])   # V part and other rows untouched
 
 
 def test_batched_sampling_is_reproducible_and_plausible():

@@ -46,5 +46,5 @@ for ns in ns_list:
         k, v = heads[i[0] % NC]; i[0] += 1
         return ops.attention(q.view(H, G, Dh), k, v, 1, 1, Dh, Dh ** -0.5, causal=False, kv_len=kl4, nsplit=ns)
     a, b = timeit(row_major), timeit(head_major)
-    print(json.dumps(dict(decode_kernel=os.environ.get("SC_ATTN_DECODE", "1"), S=S, nsplit=ns, row_major_us=round(a, 2), row_major_TBs=round(gb / a * 1e3, 2),
+    print(json.dumps(dict(S=S, nsplit=ns, row_major_us=round(a, 2), row_major_TBs=round(gb / a * 1e3, 2),
                           head_major_us=round(b, 2), head_major_TBs=round(gb / b * 1e3, 2))))

@@ -23,7 +23,7 @@ name_col = "display_name" if "display_name" in scols else ("kernel_name" if "ker
 qcol = "queue_id" if "queue_id" in dcols else None
 rows = db.execute(f"select s.{name_col}, d.start, d.end{', d.' + qcol if qcol else ''} from {kd} d join {ks} s on d.kernel_id = s.id order by d.start").fetchall()
 
-HBM = re.compile(r"k_gemv|k_decode_qkv|k_attn_decode|k_attn_merge|k_attn_combine|k_gemm_skinny|k_pick|k_sample|k_decode_advance|k_rope_qk_row|k_rope_row")
+HBM = re.compile(r"k_gemv|k_decode_qkv|k_attn_decode|k_attn_merge|k_attn_combine|k_gemm_skinny|k_pick|k_sample|k_decode_advance")
 MFMA = re.compile(r"k_gemm_fat|k_gemm256|k_gemm128|k_attn<|k_attn\b|km_|k_vit_embed_ln|k_pre_|k_bert_embed_ln|k_pool|k_rope_f32in|k_patchify")      # (k_norm runs on both sides: left out)
 
 
