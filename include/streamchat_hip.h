@@ -229,7 +229,8 @@ int sc_layernorm_f16(const void* x, int ldx, const void* gamma, const void* beta
 int sc_rmsnorm_f16(const void* x, int ldx, const void* gamma, float eps, void* y, int ldy, int rows,
                    int cols, sc_stream_t stream);
 
-/* Qwen2 helpers.  sc_gather_rows_f16: out[r] = table[ids[r]] (embed_tokens; ids < 0 -> zero row, filled by the image
+/* Qwen2 helpers.  sc_gather_rows_f16: out[r] = table[ids[r]], rows ldo >= H elements apart (embed_tokens; an id outside [0, vocab) -
+ * ids < 0 such as the -200 image sentinel, and ids >= vocab alike - gives a zero row: the sentinel rows are filled by the image
  * splice of llava_arch.py:208-343). */
 int sc_gather_rows_f16(const int32_t* ids, const void* table, void* out, int rows, int H, int ldo, int vocab,
                        sc_stream_t stream);
