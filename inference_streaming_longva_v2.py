@@ -80,6 +80,11 @@ def parse_args(argv=None):
                         "seeds from two separate generators seeded from torch.manual_seed), nothing is drawn from a generator shared by the two threads")
     p.add_argument("--memory_tree_dir", type=str, default=None,
                    help="persist the visual memory tree of every video here after each question (safetensors + JSON manifest; SURVEY 8(f).4)")
+    p.add_argument("--resume_memory_tree", type=str, default=None, metavar="DIR",
+                   help="continue the session from the newest complete checkpoint in DIR (what --memory_tree_dir writes after every answer): the "
+                        "videos and segments it covers are skipped, memory tree, short memory and host random state are restored and the run goes on "
+                        "with the next segment, appending to --save_file and memory_{n}.json.  No checkpoint in DIR: starts from the beginning, so one "
+                        "command line serves the first start and every restart.  May name the same directory as --memory_tree_dir")
     args = p.parse_args(argv)
     if args.num_beams != 1 and (args.temperature or 0) > 0:
         # the reference forwards num_beams and do_sample = (temperature > 0) to HF generate (:252-256): with both that is HF's beam SAMPLING, which
@@ -227,6 +232,55 @@ class Lookahead:
         return self.box["out"]
 
 
+def _feature_row(model):
+    """((P, D), dtype) of the feature rows the frame encoder of `model` produces (what the reader allocates its bank with)"""
+    enc = getattr(model, "frame_encoder", None)
+    if enc is None:
+        return None, None
+    tokens = enc.tower.cfg.num_patches + (0 if enc.tower.select_feature == "patch" else 1)
+    return (tokens, enc.projector.d_out), torch.float16
+
+
+def _tree_texts(nodes):
+    for n in nodes or []:
+        yield n.text
+        yield from _tree_texts(n.children)
+
+
+def _history_turns(memory, user_name):
+    return sum(len(day) for day in ((memory.get(user_name) or {}).get("history") or {}).values())
+
+
+def _truncate_session_files(save_file, memory_dir, user_name, answers, turns):
+    """--resume_memory_tree: what is on disk beyond the checkpoint (an answer written after it was taken) is dropped - that question is asked again"""
+    if os.path.exists(save_file):
+        data = json.load(open(save_file, "r", encoding="utf-8"))
+        if len(data) < answers:
+            raise SystemExit(f"--resume_memory_tree: the checkpoint stands after {answers} answers but {save_file} holds {len(data)}; "
+                             f"it is not the results file of that session")
+        if len(data) > answers:
+            with open(save_file, "w", encoding="utf-8") as f:
+                json.dump(data[:answers], f, ensure_ascii=False, indent=4)
+    elif answers:
+        raise SystemExit(f"--resume_memory_tree: the checkpoint stands after {answers} answers but {save_file} does not exist")
+    if memory_dir is None:
+        return
+    memory = json.load(open(memory_dir, "r", encoding="utf-8")) if os.path.exists(memory_dir) else {}
+    have = _history_turns(memory, user_name)
+    if have < turns:
+        raise SystemExit(f"--resume_memory_tree: the checkpoint stands after {turns} dialogue turns but {memory_dir} holds {have}")
+    if have > turns:
+        left = turns
+        hist = memory[user_name]["history"]
+        for day in list(hist):
+            hist[day] = hist[day][:left]
+            left -= len(hist[day])
+            if not hist[day]:
+                del hist[day]
+        with open(memory_dir, "w", encoding="utf-8") as f:
+            json.dump(memory, f, ensure_ascii=False, indent=4)
+
+
 def run_inference(args):
     """reference :680-933"""
     main_device = args.device
@@ -255,11 +309,35 @@ def run_inference(args):
         import copy
         look.tokenizer = copy.deepcopy(tokenizer)           # a HF fast tokenizer is not re-entrant: the look-ahead thread encodes with a copy of its own
         look.captioner.seed_generator = captioner.seed_generator
+    # ---- checkpoints (--memory_tree_dir) and resume (--resume_memory_tree): streamchat_amd/persistence.py ----
+    from streamchat_amd import persistence as PS
+    roles = {"answers": model.seed_generator, "captions": captioner.seed_generator}
+    fingerprint = PS.settings_fingerprint(args, *_feature_row(model))
+    resume, ck = None, PS.find_checkpoint(args.resume_memory_tree) if args.resume_memory_tree else None
+    if ck is not None:
+        r_nodes, r_short, r_extra, resume = PS.load_checkpoint(ck, fingerprint, device=main_device)
+        resume["tree"], resume["short"], resume["caption_texts"] = r_nodes, r_short, r_extra.get("caption_texts", [])
+        print(f"resuming from {ck}.json: video {resume['video']}, next segment {resume['next_segment']} of {resume['segments']}, "
+              f"{resume['answers']} answers so far")
     for anno in all_annotations:
         os.makedirs(args.memory_basic_dir, exist_ok=True)
         args.memory_file = "memory_{}.json".format(inference_count)
         memory_dir = os.path.join(args.memory_basic_dir, args.memory_file)
         save_file = args.save_file
+        first_segment = 0
+        if resume is not None:
+            if inference_count < resume["video"]:                # covered by the checkpoint
+                inference_count += 1
+                continue
+            if inference_count == resume["video"]:
+                _truncate_session_files(save_file, memory_dir, "User", resume["answers"], resume["turns"])
+                first_segment = resume["next_segment"]
+                if first_segment >= resume["segments"]:          # taken after the last answer of this video: go on with the next one
+                    PS.restore_host_state(resume["host_state"], roles)
+                    inference_count += 1
+                    continue
+            elif os.path.exists(memory_dir):                     # a video after the checkpoint is run from its start: with the empty dialogue memory it started with
+                json.dump({}, open(memory_dir, "w", encoding="utf-8"))
         if not os.path.exists(memory_dir):
             json.dump({}, open(memory_dir, "w", encoding="utf-8"))
         if not os.path.exists(save_file):
@@ -271,6 +349,10 @@ def run_inference(args):
         only_related_prompt = only_related_prompt_dict_ego()[language]
         memory = json.loads(open(memory_dir, "r", encoding="utf-8").read())
         user_name = "User"
+        if first_segment:
+            # the dialogue index on disk holds the vectors the session computed turn by turn: searching with them (not with the same
+            # texts embedded again as one batch) keeps the resumed rounds on the bits of the uninterrupted run
+            local_memory_qa.warm_cache_from_index(os.path.join(args.memory_basic_dir, "memory_index", f"{user_name}_index"), main_device)
         hello_msg, user_memory, memory, user_name, user_memory_index = enter_name(user_name, memory, local_memory_qa, args)
         memory_config = dict(user_memory=user_memory, user_name=user_name, user_memory_index=user_memory_index, local_memory_qa=local_memory_qa,
                              only_related_prompt=only_related_prompt, user_keyword="[|User|]", ai_keyword="[|AI|]", boot_actual_name="AI",
@@ -298,13 +380,27 @@ def run_inference(args):
                     remember_window=args.remember_window, tau=args.tau, compress_rate=args.compress_rate, chunk_size=args.chunk_size,
                     num_clusters=args.num_clusters, interval=args.interval, batch_captions=args.batch_captions)
             return feature_bank, tree, short
+        if first_segment:
+            if resume["segments"] != len(segments):
+                raise SystemExit(f"--resume_memory_tree: the checkpoint was taken in a video with {resume['segments']} questions, video {inference_count} of "
+                                 f"this run has {len(segments)}; not the same annotations")
+            long_memory_tree, short_memory_buffer = resume["tree"], resume["short"]
+            if "caption_embeddings" in resume["tensors"]:        # the retrieval's caption -> embedding table, as the session had filled it
+                for text, e in zip(resume["caption_texts"], resume["tensors"]["caption_embeddings"]):
+                    U._caption_cache.table[(id(embedding_model), text)] = e
+            PS.restore_host_state(resume["host_state"], roles)
         for si, (questions, star, end) in enumerate(segments):
+            if si < first_segment:
+                continue
             question, labels, qa_class = questions["question"], questions["answer"], questions["class"]
             ahead = look.take() if look is not None else None
             if ahead is not None:
                 feature_bank, long_memory_tree, short_memory_buffer = ahead
             else:
                 feature_bank, long_memory_tree, short_memory_buffer = read_and_update(star, end, long_memory_tree, short_memory_buffer, captioner)
+            # what the NEXT update draws from, taken before the look-ahead thread can draw: the checkpoint after this answer describes the
+            # session before the next segment is read, with or without --overlap (the answer itself draws from its role generator only)
+            host_state = PS.capture_host_state({"captions": captioner.seed_generator}) if args.memory_tree_dir else None
             gen_kw = {}
             if look is not None and si + 1 < len(segments):
                 # the next segment's reader / updater start when this answer's prefill is done, and the answer's token loop runs on the decode
@@ -328,9 +424,16 @@ def run_inference(args):
             _, _, memory, user_name, user_memory_index = enter_name(user_name, memory, local_memory_qa, args)
             memory_config["user_memory_index"] = user_memory_index
             if args.memory_tree_dir and long_memory_tree is not None:
-                from streamchat_amd.persistence import save_memory_tree
-                save_memory_tree(long_memory_tree, os.path.join(args.memory_tree_dir, f"video_{inference_count}"), short_memory_buffer,
-                                 extra=dict(time=questions["time"], question=question))
+                # (the tree and the short memory are replaced, never mutated, by an update: the look-ahead thread works on lists of its own)
+                host_state["generators"].update(PS.capture_host_state({"answers": model.seed_generator}, which=())["generators"])
+                texts = [t for t in dict.fromkeys(_tree_texts(long_memory_tree)) if (id(embedding_model), t) in U._caption_cache.table]
+                PS.save_checkpoint(args.memory_tree_dir, inference_count, long_memory_tree, short_memory_buffer, next_segment=si + 1,
+                                   segments=len(segments), frames_consumed=[0, min(total_frames, int(end * frame_rate))],
+                                   answers=len(json.load(open(save_file, "r", encoding="utf-8"))), turns=_history_turns(memory, user_name),
+                                   host_state=host_state, fingerprint=fingerprint,
+                                   extra=dict(time=questions["time"], question=question, caption_texts=texts),
+                                   extra_tensors=dict(caption_embeddings=torch.stack([U._caption_cache.table[(id(embedding_model), t)] for t in texts]))
+                                   if texts else None)
         inference_count += 1
 
 

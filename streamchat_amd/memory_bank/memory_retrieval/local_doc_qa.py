@@ -177,6 +177,21 @@ class LocalMemoryRetrieval:
                 self._cache[t] = v
         return torch.stack([self._cache[d.page_content] for d in docs])
 
+    def warm_cache_from_index(self, vs_path, device=EMBEDDING_DEVICE):
+        """Fill the text -> vector cache from an index a previous process persisted under `vs_path` (a resumed session: the documents keep
+        the vectors they were first embedded to).  Returns the number of documents taken; a missing index is none."""
+        import torch
+        jl, npy = os.path.join(vs_path, "index.jsonl"), os.path.join(vs_path, "index.npy")
+        if not (os.path.exists(jl) and os.path.exists(npy)):
+            return 0
+        texts = [json.loads(ln)["page_content"] for ln in open(jl, encoding="utf-8").read().splitlines() if ln]
+        vecs = np.load(npy)
+        if vecs.ndim != 2 or vecs.shape[0] != len(texts):
+            return 0
+        for t, v in zip(texts, torch.from_numpy(vecs).to(device)):
+            self._cache.setdefault(t, v)
+        return len(texts)
+
     def init_memory_vector_store(self, filepath, vs_path=None, user_name: str = None, cur_date: str = None):
         """Build (or rebuild) the index of `user_name`'s dialogue documents and persist it under vs_path (:196-255)."""
         paths = [filepath] if isinstance(filepath, str) else list(filepath)

@@ -304,6 +304,96 @@ class ShardedMemory:
         return views[0].clone() if len(views) == 1 else torch.cat(views, dim=0)
 
     # ---------------------------------------------------------------------------------------------
+    # persistence: rows stay on the rank that holds them - every rank writes the tensors of its own `store` to
+    # `<path>.rank<r>.safetensors`, rank 0 writes the manifest `<path>.json` (the tree with each Ref as its list of pieces, the frame
+    # ranges, the world size) once every rank's file is in place.  No rows cross ranks on save or load.
+    FORMAT = "streamchat-sharded-memory/1"
+
+    def save(self, path, short=None, extra=None):
+        """Collective: every rank calls it with the same arguments.  `short`: the Refs `update` returned as short memory (optional);
+        `extra`: JSON-able dict (rank 0's is written).  Files are written under temporary names and renamed, the manifest last."""
+        import json
+        import uuid
+        from safetensors.torch import save_file
+        ctx = self.ctx
+        save_id = broadcast_object(ctx, uuid.uuid4().hex if ctx.rank == 0 else None, src=0) if ctx.world > 1 else uuid.uuid4().hex
+        os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+        tensors = {f"{kind}.{i}": t.detach().cpu().contiguous().clone() for (kind, i), t in self.store.items()}
+        mine = f"{path}.rank{ctx.rank}.safetensors"
+        tmp = f"{mine}.tmp{os.getpid()}"
+        try:
+            save_file(tensors, tmp, metadata=dict(format=self.FORMAT, save_id=save_id, rank=str(ctx.rank), world=str(ctx.world)))
+            os.replace(tmp, mine)
+        finally:
+            if os.path.exists(tmp):
+                os.remove(tmp)
+        written = gather_objects(ctx, sorted(tensors)) if ctx.world > 1 else [sorted(tensors)]      # (also the barrier: every rank's file is in place)
+
+        def walk(nodes):
+            out = []
+            for n in nodes or []:
+                if not isinstance(n.centroids, Ref):
+                    raise TypeError(f"ShardedMemory.save: node {n.text!r:.60} holds {type(n.centroids).__name__} centroids, not a Ref")
+                out.append(dict(text=n.text, depth=int(n.depth), ref=[list(p) for p in n.centroids.pieces], labels=n.labels,
+                                text_distance=n.text_distance, image_distance=n.image_distance, children=walk(n.children)))
+            return out
+        manifest = None
+        if ctx.rank == 0:
+            (P, D), dtype, _ = self.row_shape if self.row_shape is not None else ((None, None), None, None)
+            manifest = dict(format=self.FORMAT, save_id=save_id, world=ctx.world, nodes=walk(self.tree), short=[[list(p) for p in r.pieces] for r in short or []],
+                            seg_parts=[[list(ab) for ab in parts] for parts in self.seg_parts], next_node=self.next_node,
+                            row_shape=None if P is None else [P, D], row_dtype=None if dtype is None else str(dtype), stores=written,
+                            settings=dict(chunk_size=self.chunk_size, num_clusters=self.num_clusters, interval=self.interval,
+                                          short_window=self.short_window, remember_window=self.remember_window, tau=self.tau),
+                            extra=extra or {})
+            tmp = f"{path}.json.tmp{os.getpid()}"
+            with open(tmp, "w", encoding="utf-8") as f:
+                json.dump(manifest, f, ensure_ascii=False)
+                f.flush()
+                os.fsync(f.fileno())
+            os.replace(tmp, path + ".json")
+        if ctx.world > 1:
+            gather_objects(ctx, None)                        # nobody goes on (to the next save, say) before the manifest is in place
+        return manifest
+
+    def load(self, path):
+        """Collective inverse of `save` into THIS object (same world size, same memory settings; said so otherwise): every rank reads the
+        manifest and its own tensor file.  Returns (tree, short, extra) as `update` hands them out."""
+        import json
+        from safetensors import safe_open
+        from safetensors.torch import load_file
+        ctx = self.ctx
+        with open(path + ".json", encoding="utf-8") as f:
+            m = json.load(f)
+        if m.get("format") != self.FORMAT:
+            raise ValueError(f"{path}.json: unknown sharded-memory format {m.get('format')!r}")
+        if int(m["world"]) != ctx.world:
+            raise ValueError(f"{path}.json: was saved by {m['world']} ranks, this run has {ctx.world}; a sharded memory loads only at the "
+                             f"world size it was saved at (its rows stay on the rank that held them)")
+        for k, v in m["settings"].items():
+            if getattr(self, k) != v:
+                raise ValueError(f"{path}.json: was saved with {k} = {v!r}, this ShardedMemory has {k} = {getattr(self, k)!r}")
+        mine = f"{path}.rank{ctx.rank}.safetensors"
+        with safe_open(mine, framework="pt") as f:
+            if (f.metadata() or {}).get("save_id") != m["save_id"]:
+                raise ValueError(f"{mine}: belongs to another save than {path}.json (a save was cut short)")
+        dev = ctx.device
+        tensors = load_file(mine, device=str(dev))
+        if sorted(tensors) != m["stores"][ctx.rank]:
+            raise ValueError(f"{mine}: holds {sorted(tensors)}, the manifest lists {m['stores'][ctx.rank]}")
+        self.store = {(int(k.split(".")[0]), int(k.split(".")[1])): t for k, t in tensors.items()}
+        self.seg_parts = [[tuple(ab) for ab in parts] for parts in m["seg_parts"]]
+        self.next_node = int(m["next_node"])
+        self.row_shape = None if m["row_shape"] is None else (tuple(m["row_shape"]), getattr(torch, m["row_dtype"].split(".")[-1]), dev)
+
+        def build(d):
+            n = U.MultimodalTreeNode(Ref(d["ref"]), d["text"], d["text_distance"], d["image_distance"], d["labels"], depth=d["depth"])
+            n.children = [build(c) for c in d["children"]]
+            return n
+        self.tree = [build(d) for d in m["nodes"]] or None
+        return self.tree, [Ref(p) for p in m["short"]], m["extra"]
+
+    # ---------------------------------------------------------------------------------------------
     def broadcast_refs(self, refs, src=0, capacity=None):
         """The root's retrieval decision (a list of Refs) to every rank as ONE small int64 tensor broadcast (no pickling):
         rows = (ref index, owner, kind, id, lo, hi); preceded by a one-element broadcast of the row count."""
