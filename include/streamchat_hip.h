@@ -63,6 +63,10 @@ enum { SC_OK = 0, SC_ERR_ARG = -1, SC_ERR_WORKSPACE = -2, SC_ERR_LAUNCH = -3, SC
  *      two fp64 segment tables per iteration: the data-parallel Lloyd of a merge group, bit-identical to the 1-GPU fit at any rank count)
  *   9  - sc_rope_f16, sc_rope_row_f16, sc_rope_qk_row_f16, sc_decode_qkv_f16 (rotary angles from `theta` with HF's fp16 roundings: superseded
  *      since version 3 by the fp32 table of sc_rope_table_f32 and its consumers, which are what every caller uses)
+ *      + kernel choice independent of the row count (additive: every call that was valid keeps its meaning, the number stays 9): sc_gemm_f16's
+ *      `out_f32` argument became a flag word (bit 0 = fp32 output; SC_GEMM_DISPATCH_ROWS(m) above it; 0 / 1 mean what they meant),
+ *      sc_attention_f16's flag word gained SC_ATTN_LONG_PREFILL, + sc_attention_q_block_rows: a trailing row block of a prefill GEMM /
+ *      attention launched on its own reproduces the whole launch's bits (the last layer of a last-row-only prefill, llm.Qwen2Model.forward)
  */
 #define SC_ABI_VERSION 9
 
@@ -188,14 +192,20 @@ enum { SC_EPI_NONE = 0, SC_EPI_QUICK_GELU = 1, SC_EPI_GELU_ERF = 2, SC_EPI_SWIGL
 /* SC_EPI_SWIGLU: W rows are interleaved per 4 output columns as (gate_j, gate_j+1, up_j, up_j+1); the kernel writes
  * silu(gate) * up to C[M, N/2] (Qwen2MLP act_fn(gate_proj(x)) * up_proj(x) without the [M, 2I] intermediate). */
 /* C[M,N] = epi(A[M,K] @ W[N,K]^T + bias[N]) (+ residual[M,N]).  fp16 in, fp32 accumulate (MFMA),
- * fp16 out (out_f32 = 0) or fp32 out (out_f32 = 1).  W has the torch.nn.Linear layout [N, K].
+ * fp16 out, or fp32 out with SC_GEMM_OUT_F32 in out_flags.  W has the torch.nn.Linear layout [N, K].
  * lda / ldr / ldc in elements.  Requirements: K % 64 == 0, N % 128 == 0, A and W 16-byte aligned,
  * lda % 8 == 0.  M is arbitrary.  bias and residual may be NULL.
+ * out_flags: SC_GEMM_OUT_F32 (= 1, what `out_f32 = 1` always meant) | SC_GEMM_DISPATCH_ROWS(m), m >= M: choose the kernel as for a GEMM of m rows
+ * and compute M rows.  Which kernel runs depends on the row count (M <= 32: weight-streaming kernels, M >= 1024: 256 x 256 tiles, between:
+ * 128 x 128 tiles) and the kernels round differently in the last bit; within one kernel an output element depends on its own row of A
+ * alone.  So rows [r0, r0 + M) of an m-row GEMM, launched on their own with this hint, are bit-identical to the same rows of the m-row launch.
  * Optional A row-group map (a_grp > 0): logical row m reads storage row
  * (m / a_grp) * a_grp_stride + a_grp_off + m % a_grp  — e.g. (576, 577, 1) drops the CLS token of every
  * frame (`feature_select`, reference clip_encoder.py:46-66) without a copy. */
+enum { SC_GEMM_OUT_F32 = 1 };
+#define SC_GEMM_DISPATCH_ROWS(m) ((int)(m) << 1)      /* m < 2^30 */
 int sc_gemm_f16(const void* A, int lda, const void* W, const void* bias, const void* residual, int ldr,
-                void* C, int ldc, int M, int N, int K, int epilogue, int out_f32, int a_grp,
+                void* C, int ldc, int M, int N, int K, int epilogue, int out_flags, int a_grp,
                 int a_grp_stride, int a_grp_off, sc_stream_t stream);
 
 /* The same GEMM with an epilogue that knows the output columns are HEADS of width 128 (round 3, ABI 3; served by the hand-scheduled
@@ -280,6 +290,10 @@ int sc_avgpool_tokens_f16(const void* in, void* out, int B, int P, int D, int r,
  *           bit 1 (SC_ATTN_Q_PRESCALED, ABI 3): q already carries scale * log2(e) - applied by its producer to the fp32 projection before
  *           the one rounding to fp16 (sc_gemm_headed_f16, sc_decode_qkv_tab_f16, sc_rope_f32in_f16 with a scaled table) - and `scale` is
  *           ignored: the kernel takes p = 2^(q.k - m) without a per-score multiply
+ *           bit 2 (SC_ATTN_LONG_PREFILL): run the long-prefill kernel (variant 1 of sc_attention_variant) whatever Sq is; Dh = 128 and
+ *           nsplit = 1 only.  Meant for the rows of ONE trailing q-block (sc_attention_q_block_rows) of a launch that ran that variant.
+ *           The flag only chooses the kernel: Sq is not checked against the block size, and a launch of several blocks gets no promise
+ *           beyond sc_attention_f16's own (each block is then counted from row 0 of THIS launch, not of the one it was cut from)
  *   kv_len: optional [B] int32 valid key count per batch row (padding mask) or NULL.  Dh in {32, 64, 128}.
  *   nsplit > 1: split-KV ("flash-decoding") for few queries over a long cache — the key range is cut into nsplit slices
  *   processed by separate workgroups and merged; needs ws of B*Hq*Sq*nsplit*(Dh+2)*4 bytes.  nsplit = 1: ws may be NULL.
@@ -289,7 +303,7 @@ int sc_avgpool_tokens_f16(const void* in, void* out, int B, int P, int D, int r,
  *   q_batch_stride / o_batch_stride (elements; 0 = Sq*ldq / Sq*ldo): distance between consecutive batch rows of q / out, so the
  *   head-packed addressing also works for B > 1 (batched decode: q is [B, Hq*Dh] and its batch stride is Hq*Dh, not G*Dh).
  *   k / v batch rows are Skv*ldk / Skv*ldv apart. */
-enum { SC_ATTN_CAUSAL = 1, SC_ATTN_Q_PRESCALED = 2 };
+enum { SC_ATTN_CAUSAL = 1, SC_ATTN_Q_PRESCALED = 2, SC_ATTN_LONG_PREFILL = 4 };
 int sc_attention_f16(const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, void* out,
                      int ldo, int B, int Sq, int Skv, int Hq, int Hkv, int Dh, float scale, int causal,
                      const int32_t* kv_len, int nsplit, void* ws, size_t ws_bytes, int q_head_stride,
@@ -301,6 +315,11 @@ int sc_attention_f16(const void* q, int ldq, const void* k, int ldk, const void*
  * 16 query rows, split-KV, non-causal = a decode step: every wave streams its own run of 32-row chunks).  Host-only query for tests and
  * profiles; the arithmetic contract of sc_attention_f16 does not depend on it. */
 int sc_attention_variant(int Dh, int Sq, int nsplit);
+/* Query rows of one q-block (= one workgroup) of the k_attn launch that serves the shape: 192 for variant 1, 128 for variant 0, 0 for variant 3.
+ * Blocks are counted from query row 0 of the launch; a query row's result depends on the launch only through the block it sits in, so the rows
+ * [b0, Sq) of the last block, b0 = rows * ((Sq - 1) / rows), launched on their own over the same keys (causal: aligned to the end, as always;
+ * SC_ATTN_LONG_PREFILL where the whole launch was variant 1) are bit-identical to what the whole launch writes for them.  Host-only. */
+int sc_attention_q_block_rows(int Dh, int Sq, int nsplit);
 
 /* ----------------------------------------------------------------------------------------------
  * Next-token selection over fp32 LM-head logits.  Replaces what HF `generate` does after the forward pass

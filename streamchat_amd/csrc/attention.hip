@@ -476,10 +476,22 @@ const char* sc_attn_build_tag() {
 #endif
 }
 
+// query rows per wave in 16-row blocks: the long-prefill variant and everything else (a workgroup = 4 waves = one q-block of 64 * QB rows)
+constexpr int QB_LONG = 3, QB_STD = 2;
+
 extern "C" int sc_attention_variant(int Dh, int Sq, int nsplit) {
     if (Dh == 128 && nsplit == 1 && Sq >= 2048) return 1;
     if (Dh == 128 && nsplit > 1 && Sq <= 16) return 3;      // (non-causal calls; a causal call of this shape runs k_attn)
     return 0;
+}
+
+// rows of one q-block of the k_attn launch that serves the shape (0: k_attn_decode, which has no q-blocks).  Blocks are counted from query
+// row 0 of a launch, and a query row's result depends on the launch only through the block it sits in (the block's chunk walk, its split of
+// general and steady-state tiles and its redo rule): the rows of a TRAILING block launched on their own - Sq = those rows, the same keys,
+// SC_ATTN_LONG_PREFILL where the whole launch ran that variant - leave bit for bit what the whole launch leaves in them.
+extern "C" int sc_attention_q_block_rows(int Dh, int Sq, int nsplit) {
+    const int v = sc_attention_variant(Dh, Sq, nsplit);
+    return v == 3 ? 0 : 64 * (v == 1 ? QB_LONG : QB_STD);
 }
 
 extern "C" int sc_attention_f16(const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, void* out, int ldo, int B,
@@ -487,7 +499,7 @@ extern "C" int sc_attention_f16(const void* q, int ldq, const void* k, int ldk, 
                                 int nsplit, void* ws, size_t ws_bytes, int q_head_stride, int o_head_stride, int64_t q_batch_stride,
                                 int64_t o_batch_stride, sc_stream_t stream) {
     SC_REQUIRE(q && k && v && out, "sc_attention_f16: null pointer argument");
-    SC_REQUIRE((causal_flags & ~(1 | SC_ATTN_Q_PRESCALED)) == 0, "sc_attention_f16: unknown bits in the causal / flags argument");
+    SC_REQUIRE((causal_flags & ~(1 | SC_ATTN_Q_PRESCALED | SC_ATTN_LONG_PREFILL)) == 0, "sc_attention_f16: unknown bits in the causal / flags argument");
     const int causal = causal_flags & 1;
     SC_REQUIRE(B > 0 && Sq > 0 && Skv > 0 && Hq > 0 && Hkv > 0 && Hq % Hkv == 0, "sc_attention_f16: bad sizes");
     SC_REQUIRE(Dh == 64 || Dh == 128 || Dh == 32, "sc_attention_f16: head dim %d unsupported (32, 64, 128)", Dh);
@@ -509,6 +521,9 @@ extern "C" int sc_attention_f16(const void* q, int ldq, const void* k, int ldk, 
     SC_REQUIRE(qbs % 8 == 0 && obs % 4 == 0, "sc_attention_f16: batch strides must be multiples of 8 (q) / 4 (out)");
     // few query rows against a long cache with split-KV = a decode step: the per-wave streaming kernel
     const bool pre = (causal_flags & SC_ATTN_Q_PRESCALED) != 0;
+    // the long-prefill kernel for ANY Sq: the caller runs a row block of a long launch on its own and wants that launch's arithmetic
+    const bool long_prefill = (causal_flags & SC_ATTN_LONG_PREFILL) != 0;
+    SC_REQUIRE(!long_prefill || (Dh == 128 && nsplit == 1), "sc_attention_f16: SC_ATTN_LONG_PREFILL needs Dh = 128 and nsplit = 1");
     const float sl2_dec = pre ? 1.0f : scale * 1.4426950408889634f;
     if (sc_attention_variant(Dh, Sq, nsplit) == 3 && !causal) {
         sc_attn_decode_launch(q, ldq, k, ldk, v, ldv, B, Sq, Skv, Hq, Hkv, sl2_dec, kv_len, part, nsplit, qhs, qbs, s);
@@ -516,11 +531,11 @@ extern "C" int sc_attention_f16(const void* q, int ldq, const void* k, int ldk, 
         SC_CHECK_LAUNCH("sc_attention_f16");
         return SC_OK;
     }
-    if (Dh == 64) return launch_attn<64, 2>(q, ldq, k, ldk, v, ldv, out, ldo, B, Sq, Skv, Hq, Hkv, scale, causal, kv_len, part, nsplit, qhs, ohs, qbs, obs, s, pre);
+    if (Dh == 64) return launch_attn<64, QB_STD>(q, ldq, k, ldk, v, ldv, out, ldo, B, Sq, Skv, Hq, Hkv, scale, causal, kv_len, part, nsplit, qhs, ohs, qbs, obs, s, pre);
     // long prefill: 48 queries per wave in half-tile chunks (three MFMAs per LDS fragment); everything else: 32 queries, whole tiles.
     // (The hand-scheduled one-wave-per-SIMD k_attn_fat of round 2 kept the matrix pipe busier and delivered the same TFLOP/s under the
     // board's power cap; it was removed in round 3 - see DESIGN.md section 4.)
-    if (sc_attention_variant(Dh, Sq, nsplit) == 1) return launch_attn<128, 3, 32>(q, ldq, k, ldk, v, ldv, out, ldo, B, Sq, Skv, Hq, Hkv, scale, causal, kv_len, part, nsplit, qhs, ohs, qbs, obs, s, pre);
-    if (Dh == 128) return launch_attn<128, 2>(q, ldq, k, ldk, v, ldv, out, ldo, B, Sq, Skv, Hq, Hkv, scale, causal, kv_len, part, nsplit, qhs, ohs, qbs, obs, s, pre);
-    return launch_attn<32, 2>(q, ldq, k, ldk, v, ldv, out, ldo, B, Sq, Skv, Hq, Hkv, scale, causal, kv_len, part, nsplit, qhs, ohs, qbs, obs, s, pre);
+    if (sc_attention_variant(Dh, Sq, nsplit) == 1 || long_prefill) return launch_attn<128, QB_LONG, 32>(q, ldq, k, ldk, v, ldv, out, ldo, B, Sq, Skv, Hq, Hkv, scale, causal, kv_len, part, nsplit, qhs, ohs, qbs, obs, s, pre);
+    if (Dh == 128) return launch_attn<128, QB_STD>(q, ldq, k, ldk, v, ldv, out, ldo, B, Sq, Skv, Hq, Hkv, scale, causal, kv_len, part, nsplit, qhs, ohs, qbs, obs, s, pre);
+    return launch_attn<32, QB_STD>(q, ldq, k, ldk, v, ldv, out, ldo, B, Sq, Skv, Hq, Hkv, scale, causal, kv_len, part, nsplit, qhs, ohs, qbs, obs, s, pre);
 }

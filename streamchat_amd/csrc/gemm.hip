@@ -1304,10 +1304,13 @@ bool skinny_generic() {
     return on;
 }
 
+// Md: the row count the KERNEL is chosen for (SC_GEMM_DISPATCH_ROWS; = M without it).  Every kernel below computes an output element from
+// its own row of A and its own row of W alone - the K loop, the MFMA order and the epilogue are per tile, rows past M are read as zeros (or
+// re-read, never stored) - so a row block of a larger GEMM launched on its own with Md = the larger GEMM's rows reproduces that GEMM's bits.
 template <int EPI>
-int launch_gemm(const void* A, int lda, const void* W, const void* bias, const void* R, int ldr, void* C, int ldc, int M, int N,
+int launch_gemm(const void* A, int lda, const void* W, const void* bias, const void* R, int ldr, void* C, int ldc, int M, int Md, int N,
                 int K, int out_f32, int a_grp, int a_grp_stride, int a_grp_off, hipStream_t s) {
-    if (M <= 32 && K % 128 == 0 && a_grp == 0 && ldc % 4 == 0 && (!R || ldr % 4 == 0)) {      // few rows: stream W once
+    if (Md <= 32 && K % 128 == 0 && a_grp == 0 && ldc % 4 == 0 && (!R || ldr % 4 == 0)) {      // few rows: stream W once
         const dim3 block(256);
         // the LDS-ring kernels: 16-byte aligned operands and rows
         const bool al16 = ((reinterpret_cast<uintptr_t>(A) | reinterpret_cast<uintptr_t>(W) | reinterpret_cast<uintptr_t>(R) | reinterpret_cast<uintptr_t>(bias)) & 15) == 0;
@@ -1326,7 +1329,7 @@ int launch_gemm(const void* A, int lda, const void* W, const void* bias, const v
                     sc_set_max_lds<k_gemm_skinny_l<EPI, F32, MGV, PDV>>(LDSB);                                                                                   \
                     hipLaunchKernelGGL((k_gemm_skinny_l<EPI, F32, MGV, PDV>), dim3((unsigned)gx), block, LDSB, s, (const _Float16*)A, lda, (const _Float16*)W,   \
                                        (const _Float16*)bias, (const _Float16*)R, ldr, C, ldc, M, N, K, strips / gx, strips % gx); } while (0)
-                if (M <= 16) { if (out_f32) SC_LSL(true, 1, 4); else SC_LSL(false, 1, 4); }
+                if (Md <= 16) { if (out_f32) SC_LSL(true, 1, 4); else SC_LSL(false, 1, 4); }
                 else { if (out_f32) SC_LSL(true, 2, 3); else SC_LSL(false, 2, 3); }
 #undef SC_LSL
                 SC_CHECK_LAUNCH("sc_gemm_f16");
@@ -1339,7 +1342,7 @@ int launch_gemm(const void* A, int lda, const void* W, const void* bias, const v
                     sc_set_max_lds<k_gemm_skinny_lx<EPI, F32, MGV>>(LDSB);                                                                                  \
                     hipLaunchKernelGGL((k_gemm_skinny_lx<EPI, F32, MGV>), dim3((unsigned)cus), block, LDSB, s, (const _Float16*)A, lda, (const _Float16*)W, \
                                        (const _Float16*)bias, (const _Float16*)R, ldr, C, ldc, M, N, strips / cus, strips % cus); } while (0)
-                if (M <= 16) { if (out_f32) SC_LLX(true, 1); else SC_LLX(false, 1); }
+                if (Md <= 16) { if (out_f32) SC_LLX(true, 1); else SC_LLX(false, 1); }
                 else { if (out_f32) SC_LLX(true, 2); else SC_LLX(false, 2); }
 #undef SC_LLX
                 SC_CHECK_LAUNCH("sc_gemm_f16");
@@ -1349,14 +1352,14 @@ int launch_gemm(const void* A, int lda, const void* W, const void* bias, const v
         const dim3 grid((unsigned)(N / 16));
 #define SC_LSK(F32, MGV) hipLaunchKernelGGL((k_gemm_skinny<EPI, F32, MGV>), grid, block, 0, s, (const _Float16*)A, lda, (const _Float16*)W, \
                                               (const _Float16*)bias, (const _Float16*)R, ldr, C, ldc, M, N, K)
-        if (M <= 16) { if (out_f32) SC_LSK(true, 1); else SC_LSK(false, 1); }
+        if (Md <= 16) { if (out_f32) SC_LSK(true, 1); else SC_LSK(false, 1); }
         else { if (out_f32) SC_LSK(true, 2); else SC_LSK(false, 2); }
 #undef SC_LSK
         SC_CHECK_LAUNCH("sc_gemm_f16");
         return SC_OK;
     }
     const bool wide_ok = out_f32 || (ldc % 8 == 0 && (reinterpret_cast<uintptr_t>(C) & 15) == 0);      // 16-byte epilogue stores
-    if (M >= 1024 && wide_ok && N % BN2 == 0 && K % BK2 == 0) {
+    if (Md >= 1024 && wide_ok && N % BN2 == 0 && K % BK2 == 0) {
         // fp16 output: the hand-scheduled k_gemm_fat (16-byte DMA granules; 16-byte residual rows: loads along rows + the DMA of the first row tile)
         if (!out_f32 && a_grp == 0 && K % 128 == 0 && (size_t)lda * 512 < (1ull << 31) && lda % 8 == 0 &&
             (reinterpret_cast<uintptr_t>(A) & 15) == 0 && (reinterpret_cast<uintptr_t>(W) & 15) == 0 &&
@@ -1413,9 +1416,12 @@ extern "C" int sc_gemm_headed_f16(const void* A, int lda, const void* W, const v
 }
 
 extern "C" int sc_gemm_f16(const void* A, int lda, const void* W, const void* bias, const void* residual, int ldr, void* C, int ldc,
-                           int M, int N, int K, int epilogue, int out_f32, int a_grp, int a_grp_stride, int a_grp_off, sc_stream_t stream) {
+                           int M, int N, int K, int epilogue, int out_flags, int a_grp, int a_grp_stride, int a_grp_off, sc_stream_t stream) {
     SC_REQUIRE(A && W && C, "sc_gemm_f16: null pointer argument");
     SC_REQUIRE(M > 0 && N > 0 && K > 0, "sc_gemm_f16: M, N, K must be positive");
+    // out_flags: bit 0 = fp32 output, the bits above = SC_GEMM_DISPATCH_ROWS (0: choose the kernel for M itself)
+    SC_REQUIRE(out_flags >= 0 && ((out_flags >> 1) == 0 || (out_flags >> 1) >= M), "sc_gemm_f16: SC_GEMM_DISPATCH_ROWS (%d) must be at least M (%d)", out_flags >> 1, M);
+    const int out_f32 = out_flags & SC_GEMM_OUT_F32, Md = (out_flags >> 1) ? (out_flags >> 1) : M;
     SC_REQUIRE(N % BN == 0, "sc_gemm_f16: N (%d) must be a multiple of %d", N, BN);
     SC_REQUIRE(K % BK == 0, "sc_gemm_f16: K (%d) must be a multiple of %d", K, BK);
     SC_REQUIRE(lda >= K && lda % 8 == 0 && ldc >= (epilogue == SC_EPI_SWIGLU ? N / 2 : N) && ldc % 2 == 0 && (epilogue == SC_EPI_SWIGLU || ldc % 4 == 0),
@@ -1428,12 +1434,12 @@ extern "C" int sc_gemm_f16(const void* A, int lda, const void* W, const void* bi
     SC_REQUIRE(a_grp >= 0 && (a_grp == 0 || (a_grp_stride >= a_grp && a_grp_off >= 0)), "sc_gemm_f16: bad A row-group map");
     hipStream_t s = (hipStream_t)stream;
     switch (epilogue) {
-        case SC_EPI_NONE: return launch_gemm<SC_EPI_NONE>(A, lda, W, bias, residual, ldr, C, ldc, M, N, K, out_f32, a_grp, a_grp_stride, a_grp_off, s);
-        case SC_EPI_QUICK_GELU: return launch_gemm<SC_EPI_QUICK_GELU>(A, lda, W, bias, residual, ldr, C, ldc, M, N, K, out_f32, a_grp, a_grp_stride, a_grp_off, s);
-        case SC_EPI_GELU_ERF: return launch_gemm<SC_EPI_GELU_ERF>(A, lda, W, bias, residual, ldr, C, ldc, M, N, K, out_f32, a_grp, a_grp_stride, a_grp_off, s);
+        case SC_EPI_NONE: return launch_gemm<SC_EPI_NONE>(A, lda, W, bias, residual, ldr, C, ldc, M, Md, N, K, out_f32, a_grp, a_grp_stride, a_grp_off, s);
+        case SC_EPI_QUICK_GELU: return launch_gemm<SC_EPI_QUICK_GELU>(A, lda, W, bias, residual, ldr, C, ldc, M, Md, N, K, out_f32, a_grp, a_grp_stride, a_grp_off, s);
+        case SC_EPI_GELU_ERF: return launch_gemm<SC_EPI_GELU_ERF>(A, lda, W, bias, residual, ldr, C, ldc, M, Md, N, K, out_f32, a_grp, a_grp_stride, a_grp_off, s);
         case SC_EPI_SWIGLU:
             SC_REQUIRE(!residual && !out_f32, "sc_gemm_f16: SwiGLU epilogue takes no residual and writes fp16");
-            return launch_gemm<SC_EPI_SWIGLU>(A, lda, W, bias, residual, ldr, C, ldc, M, N, K, 0, a_grp, a_grp_stride, a_grp_off, s);
+            return launch_gemm<SC_EPI_SWIGLU>(A, lda, W, bias, residual, ldr, C, ldc, M, Md, N, K, 0, a_grp, a_grp_stride, a_grp_off, s);
     }
     return sc_fail(SC_ERR_ARG, "sc_gemm_f16: unknown epilogue %d", epilogue);
 }

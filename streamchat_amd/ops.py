@@ -419,10 +419,12 @@ EPI = {"none": 0, "quick_gelu": 1, "gelu": 2, "swiglu": 3}
 
 
 def gemm(a: torch.Tensor, w: torch.Tensor, bias=None, residual=None, epilogue: str = "none", out=None, out_f32: bool = False,
-         a_rows=None, M=None):
+         a_rows=None, M=None, dispatch_rows=None):
     """out[M,N] = epi(a[M,K] @ w[N,K]^T + bias) (+ residual); fp16 operands, fp32 MFMA accumulate.
     `a` may be a row-strided view (stride(1) == 1).  a_rows=(grp, stride, off) with explicit M reads logical
-    row m from storage row (m//grp)*stride + off + m%grp."""
+    row m from storage row (m//grp)*stride + off + m%grp.
+    dispatch_rows=m (>= M): the kernel is chosen as for a GEMM of m rows (SC_GEMM_DISPATCH_ROWS) - a row block of an m-row GEMM launched
+    on its own is then bit-identical to those rows of the m-row launch."""
     _require_cuda(a, w)
     lib = _lib.load()
     if a.dtype != torch.float16 or w.dtype != torch.float16:
@@ -440,7 +442,7 @@ def gemm(a: torch.Tensor, w: torch.Tensor, bias=None, residual=None, epilogue: s
     P = lambda t: None if t is None else c_void_p(t.data_ptr())
     with torch.cuda.device(a.device), _timed("k_gemm", 2.0 * M * N * K):
         check(lib.sc_gemm_f16(P(a), a.stride(0), P(w), P(bias), P(residual), 0 if residual is None else residual.stride(0), P(out),
-                              out.stride(0), M, N, K, EPI[epilogue], 1 if out.dtype == torch.float32 else 0,
+                              out.stride(0), M, N, K, EPI[epilogue], (1 if out.dtype == torch.float32 else 0) | (int(dispatch_rows or 0) << 1),
                               *((0, 0, 0) if a_rows is None else a_rows), stream_ptr(a.device)),
               "sc_gemm_f16")
     return out
@@ -592,11 +594,18 @@ def attention_variant(Dh: int, Sq: int, nsplit: int = 1) -> int:
     return int(_lib.load().sc_attention_variant(Dh, Sq, nsplit))
 
 
+def attention_q_block_rows(Dh: int, Sq: int, nsplit: int = 1) -> int:
+    """Query rows of one q-block of the k_attn launch that serves this shape (192 long-prefill variant, 128 otherwise, 0 k_attn_decode): the one
+    place that number lives (attention.hip, sc_attention_q_block_rows)."""
+    return int(_lib.load().sc_attention_q_block_rows(Dh, Sq, nsplit))
+
+
 def attention(q, k, v, Hq: int, Hkv: int, Dh: int, scale: float, causal: bool = False, kv_len=None, out=None, nsplit: int = 1,
-              q_head_stride: int = 0, o_head_stride: int = 0, out_ld=None, ws=None, q_prescaled: bool = False):
+              q_head_stride: int = 0, o_head_stride: int = 0, out_ld=None, ws=None, q_prescaled: bool = False, long_prefill: bool = False):
     """Fused attention.  q [B, Sq, >=Hq*Dh], k/v [B, Skv, >=Hkv*Dh] fp16 (may be strided column slices of one fused
     QKV buffer: only stride(-1) == 1 and a common row stride per tensor are required).  Returns [B, Sq, Hq*Dh].
-    q_prescaled: q already carries scale * log2(e) from its producer (gemm_headed, decode_qkv_tab, rope_f32in with a scaled table)."""
+    q_prescaled: q already carries scale * log2(e) from its producer (gemm_headed, decode_qkv_tab, rope_f32in with a scaled table).
+    long_prefill: the long-prefill kernel whatever Sq is (SC_ATTN_LONG_PREFILL: the rows of a trailing q-block of a long launch on their own)."""
     _require_cuda(q, k, v)
     lib = _lib.load()
     B, Sq = q.shape[0], q.shape[1]
@@ -620,7 +629,7 @@ def attention(q, k, v, Hq: int, Hkv: int, Dh: int, scale: float, causal: bool = 
         ws = None
     with torch.cuda.device(q.device), _timed("k_attn", 4.0 * B * Hq * Sq * Skv * Dh * (0.5 if causal else 1.0)):
         check(lib.sc_attention_f16(P(q), q.stride(1), P(k), k.stride(1), P(v), v.stride(1), P(out), ldo, B, Sq, Skv, Hq, Hkv, Dh,
-                                   c_float(scale), (1 if causal else 0) | (2 if q_prescaled else 0), P(kl), nsplit, P(ws), c_size_t(0 if ws is None else ws.numel() * ws.element_size()),
+                                   c_float(scale), (1 if causal else 0) | (2 if q_prescaled else 0) | (4 if long_prefill else 0), P(kl), nsplit, P(ws), c_size_t(0 if ws is None else ws.numel() * ws.element_size()),
                                    q_head_stride, o_head_stride, c_int64(q.stride(0) if B > 1 else 0), c_int64(out.stride(0) if B > 1 else 0),
                                    stream_ptr(q.device)), "sc_attention_f16")
     return out
