@@ -219,12 +219,15 @@ def _rms(x, w, eps):
     return _st(w * _st((x.float() * torch.rsqrt(v + eps)).to(x.dtype)))      # HF Qwen2RMSNorm: fp32 inside, cast to the input dtype, then the weight
 
 
-def qwen2_logits(sd, embeds, *, heads, kv_heads, layers, head_dim, theta=1e6, eps=1e-6, last_only=False, head_chunk=None, row_chunk=None):
+def qwen2_logits(sd, embeds, *, heads, kv_heads, layers, head_dim, theta=1e6, eps=1e-6, last_only=False, head_chunk=None, row_chunk=None, taps=None):
     """logits [L, vocab] for inputs_embeds [L, H] (causal, positions 0..L-1): RMSNorm -> q/k/v (bias) -> rotate-half RoPE ->
     GQA causal attention -> o_proj -> +res -> RMSNorm -> down(silu(gate) * up) -> +res; final norm; lm_head.
     last_only: logits of the last position only ([vocab]); head_chunk: attention computed for that many heads at a time (same
     arithmetic per head; bounds the [heads, L, L] score tensor for contexts of ~10 k tokens in the composed tests); row_chunk: attention
-    for that many query rows at a time against the keys up to the chunk's last row (the 49 k-token context of the shipped geometry)."""
+    for that many query rows at a time against the keys up to the chunk's last row (the 49 k-token context of the shipped geometry).
+    taps: a list that receives one tuple per layer, (rotated K [L, kv_heads*head_dim], V [L, kv_heads*head_dim], residual stream after the
+    block [L, H]) - what a KV cache holds and what the next layer reads, at the storage points of `storage()` like everything else (the
+    last-row-only layer of `last_only` + `row_chunk` taps the one row of the stream it computes).  None: nothing is recorded."""
     L, H = embeds.shape
     x = embeds
     pos = torch.arange(L, device=x.device, dtype=torch.float32)
@@ -255,11 +258,15 @@ def qwen2_logits(sd, embeds, *, heads, kv_heads, layers, head_dim, theta=1e6, ep
             x = x[-1:] + F.linear(a.transpose(0, 1).reshape(1, heads * head_dim), sd[p + "self_attn.o_proj.weight"])
             h = _rms(x, sd[p + "post_attention_layernorm.weight"], eps)
             x = x + F.linear(F.silu(F.linear(h, sd[p + "mlp.gate_proj.weight"])) * F.linear(h, sd[p + "mlp.up_proj.weight"]), sd[p + "mlp.down_proj.weight"])
+            if taps is not None:
+                taps.append((k[::heads // kv_heads].transpose(0, 1).reshape(L, kv_heads * head_dim), v[::heads // kv_heads].transpose(0, 1).reshape(L, kv_heads * head_dim), x))
             break
         q = _st(F.linear(h, sd[p + "self_attn.q_proj.weight"], sd[p + "self_attn.q_proj.bias"])).view(L, heads, head_dim).transpose(0, 1)
         k = _st(F.linear(h, sd[p + "self_attn.k_proj.weight"], sd[p + "self_attn.k_proj.bias"])).view(L, kv_heads, head_dim).transpose(0, 1)
         v = _st(F.linear(h, sd[p + "self_attn.v_proj.weight"], sd[p + "self_attn.v_proj.bias"])).view(L, kv_heads, head_dim).transpose(0, 1)
         q, k = rot(q), rot(k)
+        if taps is not None:
+            kv_tap = (k.transpose(0, 1).reshape(L, kv_heads * head_dim), v.transpose(0, 1).reshape(L, kv_heads * head_dim))
         k = k.repeat_interleave(heads // kv_heads, dim=0)
         v = v.repeat_interleave(heads // kv_heads, dim=0)
         if row_chunk:                                  # long contexts: query rows r0..r1 against keys 0..r1 only (the masked rest is exp(-inf) = 0)
@@ -278,6 +285,8 @@ def qwen2_logits(sd, embeds, *, heads, kv_heads, layers, head_dim, theta=1e6, ep
         h = _rms(x, sd[p + "post_attention_layernorm.weight"], eps)
         m = _st(_st(F.silu(_st(F.linear(h, sd[p + "mlp.gate_proj.weight"])))) * _st(F.linear(h, sd[p + "mlp.up_proj.weight"])))
         x = _st(x + _st(F.linear(m, sd[p + "mlp.down_proj.weight"])))
+        if taps is not None:
+            taps.append(kv_tap + (x,))
     x = _rms(x[-1:] if last_only else x, sd["model.norm.weight"], eps)
     out = _st(F.linear(x, sd["lm_head.weight"] if "lm_head.weight" in sd else sd["model.embed_tokens.weight"]))
     return out[0] if last_only else out
