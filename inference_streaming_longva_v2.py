@@ -85,6 +85,10 @@ def parse_args(argv=None):
                         "videos and segments it covers are skipped, memory tree, short memory and host random state are restored and the run goes on "
                         "with the next segment, appending to --save_file and memory_{n}.json.  No checkpoint in DIR: starts from the beginning, so one "
                         "command line serves the first start and every restart.  May name the same directory as --memory_tree_dir")
+    p.add_argument("--decode_weights", type=str, choices=["fp16", "fp8"], default="fp16",
+                   help="weights the batch-1 answer decode streams: fp8 = per-output-row OCP e4m3 copies of the projections and lm_head, half the "
+                        "bytes per token (an accuracy trade, off by default: ~2.6 %% relative rms error per projection; +7.1 GB at 7B; prefill and "
+                        "batched captions stay fp16).  A decoding setting like --temperature: not part of the memory fingerprint")
     args = p.parse_args(argv)
     if args.num_beams != 1 and (args.temperature or 0) > 0:
         # the reference forwards num_beams and do_sample = (temperature > 0) to HF generate (:252-256): with both that is HF's beam SAMPLING, which
@@ -123,6 +127,13 @@ class Cv2Capture:
 
 def build_models(args):
     """Real checkpoints (default) or, with --synthetic, random-init models of the real (or --tiny) architectures."""
+    built = _build_models(args)
+    if getattr(args, "decode_weights", "fp16") == "fp8":
+        built[0].lm.enable_fp8_decode()
+    return built
+
+
+def _build_models(args):
     dev = args.device
     if not args.synthetic:
         from streamchat_amd import checkpoint as CK

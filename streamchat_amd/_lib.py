@@ -70,6 +70,15 @@ SIGNATURES = {
     "sc_sim_topk": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
 }
 
+# include/streamchat_hip_w8.h - FP8 (e4m3) weight-only decode projections: an ADDITIVE extension header (base ABI 9, the version number and
+# the table above are untouched); bound in load() like the base symbols, a library without one of them fails there, naming it
+EXT_SIGNATURES = {
+    "sc_quantize_rows_e4m3": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "sc_gemv_w8_f16": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_float, c_void_p]),
+    "sc_decode_qkv_tab_w8": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_int, c_void_p,
+                                     c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p]),
+}
+
 _lib = None
 
 
@@ -90,7 +99,7 @@ def load():
     except ImportError:
         pass
     lib = ctypes.CDLL(LIB_PATH)
-    for name, (res, args) in SIGNATURES.items():
+    for name, (res, args) in list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()):
         try:
             fn = getattr(lib, name)
         except AttributeError as e:

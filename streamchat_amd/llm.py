@@ -48,6 +48,19 @@ def random_qwen2_state_dict(cfg: Qwen2ConfigLite, seed=0, device="cuda", dtype=t
     return sd
 
 
+DECODE_WEIGHTS = ("fp16", "fp8")
+
+
+def check_decode_weights(v):
+    if v not in DECODE_WEIGHTS:
+        raise ValueError(f"decode_weights must be one of {DECODE_WEIGHTS}, got {v!r}")
+    return v
+
+
+# SC_DECODE_WEIGHTS=fp8: what Qwen2Model(decode_weights=None) means in this process (read once; the constructor argument wins)
+DEFAULT_DECODE_WEIGHTS = check_decode_weights(os.environ.get("SC_DECODE_WEIGHTS") or "fp16")
+
+
 def _h(t, device):
     return t.detach().to(device=device, dtype=torch.float16).contiguous()
 
@@ -55,8 +68,11 @@ def _h(t, device):
 class Qwen2Model:
     """Decoder stack + lm_head on the HIP kernels, with a contiguous per-layer KV cache [max_seq, 2*Hkv*Dh] (K | V)."""
 
-    def __init__(self, state_dict, cfg: Qwen2ConfigLite, device="cuda", max_seq=65536, consume=False, trim_last_layer=True):
+    def __init__(self, state_dict, cfg: Qwen2ConfigLite, device="cuda", max_seq=65536, consume=False, trim_last_layer=True, decode_weights=None):
         self.cfg, self.device, self.max_seq = cfg, torch.device(device), max_seq
+        decode_weights = check_decode_weights(decode_weights if decode_weights is not None else DEFAULT_DECODE_WEIGHTS)
+        self.w8 = None                              # enable_fp8_decode(): the e4m3 copies of the decode projections THIS object decodes from
+        self._w8_shared = {}                        # ... which every shared_view() of these weights shares (quantised once, whoever asks first)
         # ON by default: in a last_only prefill the last layer's query side (q projection, attention, o, norm, MLP) runs for the attention
         # q-block that holds the final row only; K/V still for every row.  Nothing reads the other rows (HF computes them and slices the
         # logits afterwards), and the rows that do run go through the SAME kernels with the same dispatch as the full launch, so logits and
@@ -88,6 +104,30 @@ class Qwen2Model:
         self.cache = None
         self.cache_len = 0
         self._buf_rows = 0
+        if decode_weights == "fp8":
+            self.enable_fp8_decode()
+
+    def enable_fp8_decode(self):
+        """Batch-1 decode (`_decode_one`, `DecodeGraph`) from per-output-row FP8 (OCP e4m3fn) copies of wqkv, wo, wgu, wd and lm_head: half
+        the weight bytes per token.  OPT-IN, because it is an accuracy trade: about 2.6 % relative rms error on N(0, 0.02^2) weights and on a
+        K = 3584 projection's output; the kernels themselves are exact against the dequantised weights (gemv_w8.hip).  The weights are
+        quantised once, here (ops.quantize_rows_e4m3), and kept NEXT TO the fp16 tensors - prefill, BatchDecoder and the token gather of
+        tied embeddings keep using fp16 - which costs about 7.1 GB of device memory at Qwen2-7B's widths.  The switch is per object: a
+        `shared_view()` of an fp8 model decodes from fp8, a view that enables it leaves its siblings on fp16; the fp8 tensors are shared
+        either way (quantised once).  Enable it before the first generate: a DecodeGraph captured earlier keeps the weights it was captured
+        with.  Also: Qwen2Model(..., decode_weights="fp8"), SC_DECODE_WEIGHTS=fp8."""
+        if "w8" in self._w8_shared:
+            self.w8 = self._w8_shared["w8"]
+            return self
+        dq_ = self.cfg.heads * self.cfg.head_dim
+        layers = []
+        for L in self.L:
+            (qkv, sqkv), (wo, so), (wgu, sgu), (wd, sd) = (ops.quantize_rows_e4m3(L[k]) for k in ("wqkv", "wo", "wgu", "wd"))
+            # q | k | v quantised as ONE buffer; wq / wkv are row views of the bytes and of the scales, as the fp16 ones are of wqkv
+            layers.append(dict(wqkv=qkv, sqkv=sqkv, wq=qkv[:dq_], sq=sqkv[:dq_], wkv=qkv[dq_:], skv=sqkv[dq_:], wo=wo, so=so, wgu=wgu, sgu=sgu, wd=wd, sd=sd))
+        head, shead = ops.quantize_rows_e4m3(self.lm_head)
+        self.w8 = self._w8_shared["w8"] = dict(L=layers, lm_head=head, slm_head=shead)
+        return self
 
     def embed_tokens(self, ids):
         return ops.gather_rows(ids.to(self.device).view(-1), self.embed)
@@ -285,11 +325,17 @@ def _decode_one(self, embeds):
     h = embeds.reshape(1, -1)
     nsplit = getattr(self, "_nsplit_prompt", None) or decode_nsplit(Dh, pos0)       # fixed by the prefill of this prompt (see decode_nsplit)
     tq, tk = self.rope_tabs(S)
+    w8 = self.w8                                    # enable_fp8_decode(): the same step from the e4m3 weights (gemv_w8 for every gemv)
     for l, L in enumerate(self.L):
         # RMSNorm fused into the projections; fp32 sums -> RoPE with the fp32 tables -> ONE rounding (q pre-scaled): the arithmetic of
         # k_decode_qkv (the captured graph's single launch) in three launches
-        q32 = ops.gemv(L["wq"], h, L["bq"], out_f32=True, rms_gamma=L["ln1"], rms_eps=c.eps).view(1, dq)
-        kv32 = ops.gemv(L["wkv"], h, L["bkv"], out_f32=True, rms_gamma=L["ln1"], rms_eps=c.eps).view(1, 2 * dkv)
+        if w8 is None:
+            q32 = ops.gemv(L["wq"], h, L["bq"], out_f32=True, rms_gamma=L["ln1"], rms_eps=c.eps).view(1, dq)
+            kv32 = ops.gemv(L["wkv"], h, L["bkv"], out_f32=True, rms_gamma=L["ln1"], rms_eps=c.eps).view(1, 2 * dkv)
+        else:
+            Q = w8["L"][l]
+            q32 = ops.gemv_w8(Q["wq"], Q["sq"], h, L["bq"], out_f32=True, rms_gamma=L["ln1"], rms_eps=c.eps).view(1, dq)
+            kv32 = ops.gemv_w8(Q["wkv"], Q["skv"], h, L["bkv"], out_f32=True, rms_gamma=L["ln1"], rms_eps=c.eps).view(1, 2 * dkv)
         q = ops.rope_f32in(q32, tq, c.heads, Dh, torch.empty((1, dq), dtype=torch.float16, device=self.device), 0, pos0)
         ops.rope_f32in(kv32, tk, c.kv_heads, Dh, self.cache[l][pos0:S], dkv, pos0)
         ck = self.cache[l][:S]
@@ -297,10 +343,17 @@ def _decode_one(self, embeds):
         qv = q.as_strided((1, G, Dh), (dq, Dh, 1))
         att = ops.attention(qv, ck[:, :dkv].unsqueeze(0), ck[:, dkv:].unsqueeze(0), c.kv_heads, c.kv_heads, Dh, Dh ** -0.5, causal=False,
                             nsplit=nsplit, q_head_stride=G * Dh, o_head_stride=G * Dh, out_ld=Dh, q_prescaled=True).view(1, dq)
-        h2 = ops.gemv(L["wo"], att, None, residual=h).view(1, -1)
-        m = ops.gemv(L["wgu"], h2, None, epilogue="swiglu", rms_gamma=L["ln2"], rms_eps=c.eps)
-        h = ops.gemv(L["wd"], m, None, residual=h2).view(1, -1)
+        if w8 is None:
+            h2 = ops.gemv(L["wo"], att, None, residual=h).view(1, -1)
+            m = ops.gemv(L["wgu"], h2, None, epilogue="swiglu", rms_gamma=L["ln2"], rms_eps=c.eps)
+            h = ops.gemv(L["wd"], m, None, residual=h2).view(1, -1)
+        else:
+            h2 = ops.gemv_w8(Q["wo"], Q["so"], att, None, residual=h).view(1, -1)
+            m = ops.gemv_w8(Q["wgu"], Q["sgu"], h2, None, epilogue="swiglu", rms_gamma=L["ln2"], rms_eps=c.eps)
+            h = ops.gemv_w8(Q["wd"], Q["sd"], m, None, residual=h2).view(1, -1)
     self.cache_len = S
+    if w8 is not None:
+        return ops.gemv_w8(w8["lm_head"], w8["slm_head"], h, None, out_f32=True, rms_gamma=self.norm, rms_eps=c.eps)
     return ops.gemv(self.lm_head, h, None, out_f32=True, rms_gamma=self.norm, rms_eps=c.eps)
 
 
@@ -435,19 +488,33 @@ class DecodeGraph:
         lm, c = self.lm, self.lm.cfg
         dq, dkv, Dh, G = c.heads * c.head_dim, c.kv_heads * c.head_dim, c.head_dim, c.heads // c.kv_heads
         h = ops.gather_rows(self.tok, lm.embed)
+        w8 = lm.w8                                           # Qwen2Model.enable_fp8_decode(): the w8 twin of every projection (the weights never move)
         for l, L in enumerate(lm.L):
             # q / k / v projections + RMSNorm + RoPE + KV-cache append at row `pos`: one launch (gemv.hip k_decode_qkv)
-            q = ops.decode_qkv_tab(L["wq"], L["wkv"], L["bq"], L["bkv"], h, L["ln1"], c.eps, self.q_buf, lm.cache[l], self.pos, c.heads, c.kv_heads, Dh,
-                                   self.tab_q, self.tab_k).view(1, dq)
+            if w8 is None:
+                q = ops.decode_qkv_tab(L["wq"], L["wkv"], L["bq"], L["bkv"], h, L["ln1"], c.eps, self.q_buf, lm.cache[l], self.pos, c.heads, c.kv_heads, Dh,
+                                       self.tab_q, self.tab_k).view(1, dq)
+            else:
+                Q = w8["L"][l]
+                q = ops.decode_qkv_tab_w8(Q["wq"], Q["sq"], Q["wkv"], Q["skv"], L["bq"], L["bkv"], h, L["ln1"], c.eps, self.q_buf, lm.cache[l], self.pos,
+                                          c.heads, c.kv_heads, Dh, self.tab_q, self.tab_k).view(1, dq)
             ck = lm.cache[l]
             qv = q.as_strided((1, G, Dh), (dq, Dh, 1))
             att = ops.attention(qv, ck[:, :dkv].unsqueeze(0), ck[:, dkv:].unsqueeze(0), c.kv_heads, c.kv_heads, Dh, Dh ** -0.5, causal=False,
                                 kv_len=self.len, nsplit=self.nsplit, q_head_stride=G * Dh, o_head_stride=G * Dh, out_ld=Dh, ws=self.ws_attn,
                                 q_prescaled=True).view(1, dq)
-            h2 = ops.gemv(L["wo"], att, None, residual=h).view(1, -1)
-            m = ops.gemv(L["wgu"], h2, None, epilogue="swiglu", rms_gamma=L["ln2"], rms_eps=c.eps)
-            h = ops.gemv(L["wd"], m, None, residual=h2).view(1, -1)
-        logits = ops.gemv(lm.lm_head, h, None, out_f32=True, rms_gamma=lm.norm, rms_eps=c.eps)
+            if w8 is None:
+                h2 = ops.gemv(L["wo"], att, None, residual=h).view(1, -1)
+                m = ops.gemv(L["wgu"], h2, None, epilogue="swiglu", rms_gamma=L["ln2"], rms_eps=c.eps)
+                h = ops.gemv(L["wd"], m, None, residual=h2).view(1, -1)
+            else:
+                h2 = ops.gemv_w8(Q["wo"], Q["so"], att, None, residual=h).view(1, -1)
+                m = ops.gemv_w8(Q["wgu"], Q["sgu"], h2, None, epilogue="swiglu", rms_gamma=L["ln2"], rms_eps=c.eps)
+                h = ops.gemv_w8(Q["wd"], Q["sd"], m, None, residual=h2).view(1, -1)
+        if w8 is None:
+            logits = ops.gemv(lm.lm_head, h, None, out_f32=True, rms_gamma=lm.norm, rms_eps=c.eps)
+        else:
+            logits = ops.gemv_w8(w8["lm_head"], w8["slm_head"], h, None, out_f32=True, rms_gamma=lm.norm, rms_eps=c.eps)
         sp = self.sampling                                                   # HIP next-token kernels over the 152 064 logits (sampling.hip)
         u = ops.counter_uniform(self.seed, self.cnt, 1, out=self.u) if sp.temperature > 0 else None      # token n = cnt + 1 (the first was picked by the caller)
         if sp.plain:

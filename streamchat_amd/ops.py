@@ -766,6 +766,65 @@ def decode_qkv_tab(wq, wkv, bq, bkv, x, rms_gamma, rms_eps: float, q_out, cache,
     return q_out
 
 
+def _w8_operands(q, scale, what):
+    if q.dtype != torch.uint8 or scale.dtype != torch.float32 or q.dim() != 2 or scale.shape != (q.shape[0],):
+        raise StreamChatHipError(f"{what}: weights must be e4m3 bytes (uint8 [N, K]) with one fp32 scale per row")
+
+
+def quantize_rows_e4m3(w):
+    """fp16 [N, K] (rows may be strided) -> (q uint8 [N, K]: OCP e4m3fn bytes, scale fp32 [N]): per-row `amax / 448` scales, the bits of
+    `(w.float() / scale[:, None]).clamp(-448, 448).to(torch.float8_e4m3fn)` on the CPU.  Runs once per weight at load
+    (llm.Qwen2Model.enable_fp8_decode); `q.view(torch.float8_e4m3fn).float() * scale[:, None]` are the weights the w8 kernels compute with."""
+    _require_cuda(w)
+    if w.dtype != torch.float16 or w.dim() != 2 or w.stride(1) != 1:
+        raise StreamChatHipError("quantize_rows_e4m3: fp16 [N, K] with unit column stride")
+    N, K = w.shape
+    q = torch.empty((N, K), dtype=torch.uint8, device=w.device)
+    scale = torch.empty(N, dtype=torch.float32, device=w.device)
+    from ctypes import c_void_p
+    with torch.cuda.device(w.device):
+        check(_lib.load().sc_quantize_rows_e4m3(c_void_p(w.data_ptr()), w.stride(0), N, K, ptr(q), ptr(scale), stream_ptr(w.device)), "sc_quantize_rows_e4m3")
+    return q, scale
+
+
+def gemv_w8(q, scale, x, bias=None, residual=None, epilogue: str = "none", out=None, out_f32: bool = False, out_row=None, rms_gamma=None, rms_eps=1e-6):
+    """`gemv` with e4m3 weight bytes and per-row scales (quantize_rows_e4m3): y[n] = scale[n] * (q[n] . x) (+ bias) (+ residual) - half the
+    weight bytes of the batch-1 decode projection."""
+    _require_cuda(q, scale, x)
+    _w8_operands(q, scale, "gemv_w8")
+    lib = _lib.load()
+    N, K = q.shape
+    x = x.reshape(-1)
+    n_out = N // 2 if epilogue == "swiglu" else N
+    if out is None:
+        out = torch.empty(n_out, dtype=torch.float32 if out_f32 else torch.float16, device=q.device)
+    from ctypes import c_void_p
+    res = None if residual is None else ptr(residual.reshape(-1))
+    with torch.cuda.device(q.device), _timed("k_gemv_w8", 2.0 * N * K):
+        if out_row is not None:                 # `out` is a [rows, ld] buffer; the row index lives on the device
+            check(lib.sc_gemv_w8_f16(ptr(q), ptr(scale), ptr(x), ptr(bias), res, c_void_p(out.data_ptr()), N, K, EPI[epilogue], 0, ptr(out_row), out.stride(0),
+                                     ptr(rms_gamma), c_float(rms_eps), stream_ptr(q.device)), "sc_gemv_w8_f16")
+        else:
+            check(lib.sc_gemv_w8_f16(ptr(q), ptr(scale), ptr(x), ptr(bias), res, ptr(out.reshape(-1)), N, K, EPI[epilogue], 1 if out.dtype == torch.float32 else 0,
+                                     None, 0, ptr(rms_gamma), c_float(rms_eps), stream_ptr(q.device)), "sc_gemv_w8_f16")
+    return out
+
+
+def decode_qkv_tab_w8(wq, sq, wkv, skv, bq, bkv, x, rms_gamma, rms_eps: float, q_out, cache, row_index, q_heads: int, kv_heads: int, Dh: int, tab_q, tab_k):
+    """`decode_qkv_tab` with e4m3 weight bytes and per-row scales.  Bit-identical to gemv_w8(out_f32) + rope_f32in."""
+    _require_cuda(wq, sq, wkv, skv, x, q_out, cache, row_index, tab_q, tab_k)
+    _w8_operands(wq, sq, "decode_qkv_tab_w8")
+    _w8_operands(wkv, skv, "decode_qkv_tab_w8")
+    lib = _lib.load()
+    from ctypes import c_void_p
+    with torch.cuda.device(x.device), _timed("k_gemv_w8", 2.0 * (wq.shape[0] + wkv.shape[0]) * wq.shape[1]):
+        check(lib.sc_decode_qkv_tab_w8(ptr(wq), ptr(sq), ptr(wkv), ptr(skv), ptr(bq), ptr(bkv), ptr(x.reshape(-1)), ptr(rms_gamma), c_float(rms_eps),
+                                       c_void_p(q_out.data_ptr()), c_void_p(cache.data_ptr()), cache.stride(0), ptr(row_index), q_heads, kv_heads, Dh, wq.shape[1],
+                                       c_void_p(tab_q.data_ptr()), c_void_p(tab_k.data_ptr()), int(min(tab_q.shape[0], tab_k.shape[0])), stream_ptr(x.device)),
+              "sc_decode_qkv_tab_w8")
+    return q_out
+
+
 def decode_advance(nxt, ring, cnt, tok, pos, kv_len, nprev):
     """one launch: ring[cnt] = nxt; tok = nxt; cnt, pos, kv_len, nprev += 1 (device scalars of a captured decode step)"""
     _require_cuda(nxt, ring, cnt, tok, pos, kv_len, nprev)
