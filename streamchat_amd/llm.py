@@ -9,6 +9,7 @@ utiles.py:556,605); here the prompt is prefilled once into a resident KV cache a
 (greedy outputs are identical with and without a cache — SURVEY.md Appendix D)."""
 import types
 import os
+import threading
 import typing
 
 import torch
@@ -61,6 +62,16 @@ def check_decode_weights(v):
 DEFAULT_DECODE_WEIGHTS = check_decode_weights(os.environ.get("SC_DECODE_WEIGHTS") or "fp16")
 
 
+# a layer's decode projections and, in Qwen2Model.w8["L"][l], the key of each one's per-row scales
+_W8_SCALES = dict(wq="sq", wkv="skv", wo="so", wgu="sgu", wd="sd")
+
+
+def _gemv(P, x, bias=None, **kw):
+    """ops.gemv from P = (weight, None), ops.gemv_w8 from P = (e4m3 bytes, scales): see Qwen2Model._decode_proj"""
+    w, scale = P
+    return ops.gemv(w, x, bias, **kw) if scale is None else ops.gemv_w8(w, scale, x, bias, **kw)
+
+
 def _h(t, device):
     return t.detach().to(device=device, dtype=torch.float16).contiguous()
 
@@ -104,6 +115,7 @@ class Qwen2Model:
         self.cache = None
         self.cache_len = 0
         self._buf_rows = 0
+        self._b = self._f32_scratch = self._nsplit_prompt = None      # activation buffers, fp32 projection scratch, split-KV factor of the prompt
         if decode_weights == "fp8":
             self.enable_fp8_decode()
 
@@ -163,7 +175,7 @@ class Qwen2Model:
         # fp32 projections + k_rope_f32in (other head dims, short prompts, unaligned views): in row blocks through ONE reused fp32 scratch,
         # so that a long prefill on a non-7B shape does not materialise [n, dq] + [n, 2 dkv] fp32 per layer (0.7 GB at 49 k x 3584)
         RB = 4096
-        if getattr(self, "_f32_scratch", None) is None or self._f32_scratch.shape[0] < min(n, RB) or self._f32_scratch.shape[1] < max(dq, 2 * dkv):
+        if self._f32_scratch is None or self._f32_scratch.shape[0] < min(n, RB) or self._f32_scratch.shape[1] < max(dq, 2 * dkv):
             self._f32_scratch = torch.empty((min(max(n, 1), RB), max(dq, 2 * dkv)), dtype=torch.float32, device=x.device)
         for r0 in range(0, n, RB):
             r1 = min(n, r0 + RB)
@@ -227,9 +239,10 @@ class Qwen2Model:
                 # launch takes (dispatch_rows / long_prefill): those rows leave bit for bit what the untrimmed layer leaves in them.
                 b0, long_prefill = last_q_block(n, Dh)
                 # (The trim this one replaced ran the final row alone through the decode-side kernels - logits equal to a tolerance only - and
-                #  called the causal split-KV attention with the factor below.  Nothing here uses it any more; the line stays because
-                #  tests/_attn_cases.py evaluates it, from this method's source, to size its single-row causal split-KV attention cases,
-                #  which remain as coverage of that kernel path.)
+                #  called the causal split-KV attention with the factor below.  Nothing uses it any more: tests/_attn_cases.py, which sizes its
+                #  single-row causal split-KV cases with this factor, now holds the formula itself.  The line is to go with the next change; it
+                #  outlives this one only because the previous commit's tests/_attn_cases.py evaluates it from this method's source, and that
+                #  suite has to keep collecting against this tree.)
                 nsplit = max(1, min(128, ((S + 63) // 64) // 2))
                 tq, tk = self.rope_tabs(S)
                 ops.gemm_headed(x, L["wkv"], L["bkv"], self.cache[l][pos0:S], "rope", dkv, tk, pos0)
@@ -255,6 +268,58 @@ class Qwen2Model:
         xn = ops.rmsnorm(h[n - 1:n] if last_only else h, self.norm, c.eps)
         logits = ops.gemm(xn, self.lm_head, None, out_f32=True)
         return logits[0] if last_only else logits
+
+    # ---- the batch-1 decode step.  The eager loop (_decode_one) and the captured one (DecodeGraph._body) differ in how q / k / v are projected
+    # and where the cache position comes from; everything after that is the SAME code below, from whichever weights this object decodes from.
+    def _decode_proj(self, l):
+        """layer l's decode projections as name -> (weight, scale or None): the fp16 tensors, or after enable_fp8_decode() the e4m3 bytes with
+        their per-row scales (biases and norm weights are the fp16 ones either way)"""
+        if self.w8 is None:
+            return {k: (self.L[l][k], None) for k in _W8_SCALES}
+        Q = self.w8["L"][l]
+        return {k: (Q[k], Q[s]) for k, s in _W8_SCALES.items()}
+
+    def _decode_attention(self, q, ck, nsplit, kv_len=None, ws=None):
+        """split-KV attention of one token's q [1, dq] over the cache view ck: the G heads of a KV group become G query ROWS of that KV head
+        purely by addressing (row stride Dh, head stride G*Dh), so each K/V byte is read once"""
+        c = self.cfg
+        dq, dkv, Dh, G = c.heads * c.head_dim, c.kv_heads * c.head_dim, c.head_dim, c.heads // c.kv_heads
+        qv = q.as_strided((1, G, Dh), (dq, Dh, 1))
+        return ops.attention(qv, ck[:, :dkv].unsqueeze(0), ck[:, dkv:].unsqueeze(0), c.kv_heads, c.kv_heads, Dh, Dh ** -0.5, causal=False,
+                             kv_len=kv_len, nsplit=nsplit, q_head_stride=G * Dh, o_head_stride=G * Dh, out_ld=Dh, ws=ws, q_prescaled=True).view(1, dq)
+
+    def _decode_tail(self, l, P, h, att):
+        """o projection + residual, gate/up with the fused RMSNorm and SwiGLU, down projection + residual -> the layer's output [1, H]"""
+        L, c = self.L[l], self.cfg
+        h2 = _gemv(P["wo"], att, None, residual=h).view(1, -1)
+        m = _gemv(P["wgu"], h2, None, epilogue="swiglu", rms_gamma=L["ln2"], rms_eps=c.eps)
+        return _gemv(P["wd"], m, None, residual=h2).view(1, -1)
+
+    def _decode_logits(self, h):
+        """final RMSNorm fused into the lm_head GEMV -> fp32 logits [vocab]"""
+        P = (self.lm_head, None) if self.w8 is None else (self.w8["lm_head"], self.w8["slm_head"])
+        return _gemv(P, h, None, out_f32=True, rms_gamma=self.norm, rms_eps=self.cfg.eps)
+
+    def _decode_one(self, embeds):
+        """One decode step (batch 1): every projection is a GEMV that streams its weights once (HBM-bound), attention is split-KV
+        over the cache with the G = Hq/Hkv query heads of a KV group packed as G query rows (so each K/V byte is read once)."""
+        c = self.cfg
+        pos0, S = self.cache_len, self.cache_len + 1
+        dq, dkv, Dh = c.heads * c.head_dim, c.kv_heads * c.head_dim, c.head_dim
+        h = embeds.reshape(1, -1)
+        nsplit = self._nsplit_prompt or decode_nsplit(Dh, pos0)       # fixed by the prefill of this prompt (see decode_nsplit)
+        tq, tk = self.rope_tabs(S)
+        for l, L in enumerate(self.L):
+            P = self._decode_proj(l)
+            # RMSNorm fused into the projections; fp32 sums -> RoPE with the fp32 tables -> ONE rounding (q pre-scaled): the arithmetic of
+            # k_decode_qkv (the captured graph's single launch) in three launches
+            q32 = _gemv(P["wq"], h, L["bq"], out_f32=True, rms_gamma=L["ln1"], rms_eps=c.eps).view(1, dq)
+            kv32 = _gemv(P["wkv"], h, L["bkv"], out_f32=True, rms_gamma=L["ln1"], rms_eps=c.eps).view(1, 2 * dkv)
+            q = ops.rope_f32in(q32, tq, c.heads, Dh, torch.empty((1, dq), dtype=torch.float16, device=self.device), 0, pos0)
+            ops.rope_f32in(kv32, tk, c.kv_heads, Dh, self.cache[l][pos0:S], dkv, pos0)
+            h = self._decode_tail(l, P, h, self._decode_attention(q, self.cache[l][:S], nsplit))
+        self.cache_len = S
+        return self._decode_logits(h)
 
 
 def splice_image_embeddings(ids, embed_table, image_features, max_len=None, labels=None):
@@ -316,48 +381,19 @@ def decode_nsplit(head_dim: int, cache_len: int) -> int:
     return max(1, min(128, ((cache_len + 63) // 64) // 6))
 
 
-def _decode_one(self, embeds):
-    """One decode step (batch 1): every projection is a GEMV that streams its weights once (HBM-bound), attention is split-KV
-    over the cache with the G = Hq/Hkv query heads of a KV group packed as G query rows (so each K/V byte is read once)."""
-    c = self.cfg
-    pos0, S = self.cache_len, self.cache_len + 1
-    dq, dkv, Dh, G = c.heads * c.head_dim, c.kv_heads * c.head_dim, c.head_dim, c.heads // c.kv_heads
-    h = embeds.reshape(1, -1)
-    nsplit = getattr(self, "_nsplit_prompt", None) or decode_nsplit(Dh, pos0)       # fixed by the prefill of this prompt (see decode_nsplit)
-    tq, tk = self.rope_tabs(S)
-    w8 = self.w8                                    # enable_fp8_decode(): the same step from the e4m3 weights (gemv_w8 for every gemv)
-    for l, L in enumerate(self.L):
-        # RMSNorm fused into the projections; fp32 sums -> RoPE with the fp32 tables -> ONE rounding (q pre-scaled): the arithmetic of
-        # k_decode_qkv (the captured graph's single launch) in three launches
-        if w8 is None:
-            q32 = ops.gemv(L["wq"], h, L["bq"], out_f32=True, rms_gamma=L["ln1"], rms_eps=c.eps).view(1, dq)
-            kv32 = ops.gemv(L["wkv"], h, L["bkv"], out_f32=True, rms_gamma=L["ln1"], rms_eps=c.eps).view(1, 2 * dkv)
-        else:
-            Q = w8["L"][l]
-            q32 = ops.gemv_w8(Q["wq"], Q["sq"], h, L["bq"], out_f32=True, rms_gamma=L["ln1"], rms_eps=c.eps).view(1, dq)
-            kv32 = ops.gemv_w8(Q["wkv"], Q["skv"], h, L["bkv"], out_f32=True, rms_gamma=L["ln1"], rms_eps=c.eps).view(1, 2 * dkv)
-        q = ops.rope_f32in(q32, tq, c.heads, Dh, torch.empty((1, dq), dtype=torch.float16, device=self.device), 0, pos0)
-        ops.rope_f32in(kv32, tk, c.kv_heads, Dh, self.cache[l][pos0:S], dkv, pos0)
-        ck = self.cache[l][:S]
-        # the G heads of a KV group become G query ROWS of that KV head purely by addressing (row stride Dh, head stride G*Dh)
-        qv = q.as_strided((1, G, Dh), (dq, Dh, 1))
-        att = ops.attention(qv, ck[:, :dkv].unsqueeze(0), ck[:, dkv:].unsqueeze(0), c.kv_heads, c.kv_heads, Dh, Dh ** -0.5, causal=False,
-                            nsplit=nsplit, q_head_stride=G * Dh, o_head_stride=G * Dh, out_ld=Dh, q_prescaled=True).view(1, dq)
-        if w8 is None:
-            h2 = ops.gemv(L["wo"], att, None, residual=h).view(1, -1)
-            m = ops.gemv(L["wgu"], h2, None, epilogue="swiglu", rms_gamma=L["ln2"], rms_eps=c.eps)
-            h = ops.gemv(L["wd"], m, None, residual=h2).view(1, -1)
-        else:
-            h2 = ops.gemv_w8(Q["wo"], Q["so"], att, None, residual=h).view(1, -1)
-            m = ops.gemv_w8(Q["wgu"], Q["sgu"], h2, None, epilogue="swiglu", rms_gamma=L["ln2"], rms_eps=c.eps)
-            h = ops.gemv_w8(Q["wd"], Q["sd"], m, None, residual=h2).view(1, -1)
-    self.cache_len = S
-    if w8 is not None:
-        return ops.gemv_w8(w8["lm_head"], w8["slm_head"], h, None, out_f32=True, rms_gamma=self.norm, rms_eps=c.eps)
-    return ops.gemv(self.lm_head, h, None, out_f32=True, rms_gamma=self.norm, rms_eps=c.eps)
+def batched_decode_nsplit(B: int, kv_heads: int, longest: int) -> int:
+    """split-KV factor of the batched decode step (BatchDecoder) over B sequences, the longest of which ends with `longest` keys: ~10
+    workgroups per CU over the whole launch (B x KV heads x splits), at least ~24 chunks of 32 rows per workgroup.  Round 4 took the batch-1
+    rule (64 splits): 6656 workgroups of < 3 chunks per wave at 26 x 22.7 k - the launch was its own prologue, merge and 64-partial combine
+    (15.6 -> 11.5 ms per step at 24 splits, profiles/r05_*)."""
+    return max(1, min(64, ((longest + 31) // 32) // 24, -(-10 * 256 // (B * kv_heads))))
 
 
-Qwen2Model._decode_one = _decode_one
+def _eos_list(eos_token_id):
+    """HF allows one id, a list of ids or None"""
+    if isinstance(eos_token_id, (list, tuple, set)):
+        return eos_token_id
+    return [] if eos_token_id is None else [eos_token_id]
 
 
 def _lib_pick_bytes(B):
@@ -372,15 +408,33 @@ _UNSET = object()
 # addresses, not its CUs (profiles/r05_run_m_*).  128 B of padding per row (2176 B apart) walks the slots: +1.4 % tokens/s at a 49 k context in
 # the real token loop, interleaved on two boxes (325.2 -> 329.8 and 325.5 -> 330.3; 64 B: +0.2 %, 192 - 512 B: +1.0 - 1.3 %), the prefill unchanged,
 # results bit-identical (profiles/r06_run_k_kv_row_padding.md).  Every kernel takes the row stride, so the cache is a view of the padded rows.
-import os as _os
-KV_ROW_PAD = int(_os.environ.get("SC_KV_PAD", "64"))
+KV_ROW_PAD = int(os.environ.get("SC_KV_PAD", "64"))
 
 # The default CUDA generator of a device has ONE capture state: while a host thread captures a graph (torch.cuda.graph puts the generator into
 # capture mode, whether or not the graph draws from it), a draw or the replay of a sampling graph on ANOTHER host thread fails ("... during
 # capture").  Since round 5 two host threads generate at the same time (session.py, the entry point's --overlap: the answer on one, the chunk
 # captions on the other): captures, eager draws and sampling replays take this lock.  Uncontended it costs ~0.1 us per replay.
-import threading as _threading
-_GEN_LOCK = _threading.RLock()
+_GEN_LOCK = threading.RLock()
+
+
+def _capture_graph(dev, body, state):
+    """(hipGraph of one call of `body`, what that call returned).  `body` runs twice - once on a side stream outside capture (workspaces,
+    function attributes), once captured - and neither run is meant to have happened: the device tensors of `state` (the counters the body
+    advances) are put back after each."""
+    snap = tuple(t.clone() for t in state)
+    restore = lambda: [t.copy_(v) for t, v in zip(state, snap)]
+    s = torch.cuda.Stream(device=dev)
+    s.wait_stream(torch.cuda.current_stream(dev))
+    with torch.cuda.stream(s):
+        body()
+    torch.cuda.current_stream(dev).wait_stream(s)
+    restore()
+    graph = torch.cuda.CUDAGraph()
+    # (thread_local: another host thread may be driving its own stream, session.py; _GEN_LOCK: see its definition)
+    with _GEN_LOCK, torch.cuda.graph(graph, capture_error_mode="thread_local"):
+        result = body()
+    restore()
+    return graph, result
 
 
 # Round 6: SAMPLING draws nothing from a generator on the device any more.  Every sequence gets a 63-bit SEED when its generate starts and the
@@ -486,35 +540,16 @@ class DecodeGraph:
 
     def _body(self):
         lm, c = self.lm, self.lm.cfg
-        dq, dkv, Dh, G = c.heads * c.head_dim, c.kv_heads * c.head_dim, c.head_dim, c.heads // c.kv_heads
+        dq = c.heads * c.head_dim
         h = ops.gather_rows(self.tok, lm.embed)
-        w8 = lm.w8                                           # Qwen2Model.enable_fp8_decode(): the w8 twin of every projection (the weights never move)
         for l, L in enumerate(lm.L):
+            P = lm._decode_proj(l)
             # q / k / v projections + RMSNorm + RoPE + KV-cache append at row `pos`: one launch (gemv.hip k_decode_qkv)
-            if w8 is None:
-                q = ops.decode_qkv_tab(L["wq"], L["wkv"], L["bq"], L["bkv"], h, L["ln1"], c.eps, self.q_buf, lm.cache[l], self.pos, c.heads, c.kv_heads, Dh,
-                                       self.tab_q, self.tab_k).view(1, dq)
-            else:
-                Q = w8["L"][l]
-                q = ops.decode_qkv_tab_w8(Q["wq"], Q["sq"], Q["wkv"], Q["skv"], L["bq"], L["bkv"], h, L["ln1"], c.eps, self.q_buf, lm.cache[l], self.pos,
-                                          c.heads, c.kv_heads, Dh, self.tab_q, self.tab_k).view(1, dq)
-            ck = lm.cache[l]
-            qv = q.as_strided((1, G, Dh), (dq, Dh, 1))
-            att = ops.attention(qv, ck[:, :dkv].unsqueeze(0), ck[:, dkv:].unsqueeze(0), c.kv_heads, c.kv_heads, Dh, Dh ** -0.5, causal=False,
-                                kv_len=self.len, nsplit=self.nsplit, q_head_stride=G * Dh, o_head_stride=G * Dh, out_ld=Dh, ws=self.ws_attn,
-                                q_prescaled=True).view(1, dq)
-            if w8 is None:
-                h2 = ops.gemv(L["wo"], att, None, residual=h).view(1, -1)
-                m = ops.gemv(L["wgu"], h2, None, epilogue="swiglu", rms_gamma=L["ln2"], rms_eps=c.eps)
-                h = ops.gemv(L["wd"], m, None, residual=h2).view(1, -1)
-            else:
-                h2 = ops.gemv_w8(Q["wo"], Q["so"], att, None, residual=h).view(1, -1)
-                m = ops.gemv_w8(Q["wgu"], Q["sgu"], h2, None, epilogue="swiglu", rms_gamma=L["ln2"], rms_eps=c.eps)
-                h = ops.gemv_w8(Q["wd"], Q["sd"], m, None, residual=h2).view(1, -1)
-        if w8 is None:
-            logits = ops.gemv(lm.lm_head, h, None, out_f32=True, rms_gamma=lm.norm, rms_eps=c.eps)
-        else:
-            logits = ops.gemv_w8(w8["lm_head"], w8["slm_head"], h, None, out_f32=True, rms_gamma=lm.norm, rms_eps=c.eps)
+            (wq, sq), (wkv, skv) = P["wq"], P["wkv"]
+            rest = (L["bq"], L["bkv"], h, L["ln1"], c.eps, self.q_buf, lm.cache[l], self.pos, c.heads, c.kv_heads, c.head_dim, self.tab_q, self.tab_k)
+            q = (ops.decode_qkv_tab(wq, wkv, *rest) if sq is None else ops.decode_qkv_tab_w8(wq, sq, wkv, skv, *rest)).view(1, dq)
+            h = lm._decode_tail(l, P, h, lm._decode_attention(q, lm.cache[l], self.nsplit, kv_len=self.len, ws=self.ws_attn))
+        logits = lm._decode_logits(h)
         sp = self.sampling                                                   # HIP next-token kernels over the 152 064 logits (sampling.hip)
         u = ops.counter_uniform(self.seed, self.cnt, 1, out=self.u) if sp.temperature > 0 else None      # token n = cnt + 1 (the first was picked by the caller)
         if sp.plain:
@@ -532,24 +567,8 @@ class DecodeGraph:
         self.hist[0] = int(first_token); self.nprev.fill_(1); self.seed.fill_(int(seed))
 
     def capture(self):
-        with _GEN_LOCK:                 # (the capture puts the device's default generator into capture mode: see _GEN_LOCK)
-            self._capture()
-
-    def _capture(self):
-        snap = (self.tok.clone(), self.pos.clone(), self.len.clone(), self.cnt.clone(), self.nprev.clone())
-        s = torch.cuda.Stream(device=self.lm.device)
-        s.wait_stream(torch.cuda.current_stream(self.lm.device))
-        with torch.cuda.stream(s):                          # warm-up outside capture (workspaces, function attributes)
-            self._body()
-        torch.cuda.current_stream(self.lm.device).wait_stream(s)
-        for t, v in zip((self.tok, self.pos, self.len, self.cnt, self.nprev), snap):
-            t.copy_(v)
-        self.graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(self.graph, capture_error_mode="thread_local"):      # (another host thread may be driving its own stream: session.py)
-            self.logits = self._body()
+        self.graph, self.logits = _capture_graph(self.lm.device, self._body, (self.tok, self.pos, self.len, self.cnt, self.nprev))
         self._captured_ptrs = self._ptrs()
-        for t, v in zip((self.tok, self.pos, self.len, self.cnt, self.nprev), snap):
-            t.copy_(v)
 
     def run(self, n_tokens: int, eos=(), check_every: int = 16):
         """up to n tokens; returns them as a CPU list and advances lm.cache_len.  Without `eos` there is ONE host sync at the end;
@@ -611,7 +630,7 @@ class BatchDecoder:
         first_logits = []
         # (forward() also records the split-KV factor of "the prompt in the cache": it belongs to the saved state - ADVICE r04 - or an eager
         #  decode that continues the earlier prompt would merge its partials in another grouping than a DecodeGraph built for it)
-        saved = (lm.cache, lm.cache_len, lm.max_seq, getattr(lm, "_nsplit_prompt", None))
+        saved = (lm.cache, lm.cache_len, lm.max_seq, lm._nsplit_prompt)
         try:
             for b, e in enumerate(prompts):
                 lm.cache, lm.cache_len, lm.max_seq = [cl[b] for cl in self.cache], 0, self.cap
@@ -661,7 +680,7 @@ class BatchDecoder:
         """what `step()` needs when it is driven from outside `generate()` (beam search): the split-KV factor and its workspace"""
         B, dev, c = self.B, self.lm.device, self.lm.cfg
         longest = int(self.len.max().item()) + max_new_tokens
-        self.nsplit = getattr(self, "nsplit_override", None) or max(1, min(64, ((longest + 31) // 32) // 24, -(-10 * 256 // (B * c.kv_heads))))
+        self.nsplit = getattr(self, "nsplit_override", None) or batched_decode_nsplit(B, c.kv_heads, longest)
         self._ws_attn = torch.empty(max(ops.attention_workspace_bytes(B, c.kv_heads, c.heads // c.kv_heads, self.nsplit, c.head_dim), 256),
                                     dtype=torch.uint8, device=dev)
 
@@ -700,16 +719,8 @@ class BatchDecoder:
         self.seed = draw_seeds(B, generator, seed).to(dev)
         self._u = torch.zeros(B, dtype=torch.float32, device=dev)
         sp = sampling if sampling is not None else Sampling(float(temperature) if do_sample and temperature > 0 else 0.0)
-        eos = set(eos_token_id) if isinstance(eos_token_id, (list, tuple, set)) else (set() if eos_token_id is None else {eos_token_id})   # HF allows a list
-        longest = int(self.len.max().item()) + max_new_tokens
-        # split-KV factor of the batched step: ~10 workgroups per CU over the whole launch (B x KV heads x splits), at least ~24 chunks of 32
-        # rows per workgroup.  Round 4 took the batch-1 rule (64 splits): 6656 workgroups of < 3 chunks per wave at 26 x 22.7 k - the launch
-        # was its own prologue, merge and 64-partial combine (15.6 -> 11.5 ms per step at 24 splits, profiles/r05_*)
-        c_ = self.lm.cfg
-        self.nsplit = getattr(self, "nsplit_override", None) or max(1, min(64, ((longest + 31) // 32) // 24, -(-10 * 256 // (B * c_.kv_heads))))
-        c = self.lm.cfg
-        self._ws_attn = torch.empty(max(ops.attention_workspace_bytes(B, c.kv_heads, c.heads // c.kv_heads, self.nsplit, c.head_dim), 256),
-                                    dtype=torch.uint8, device=dev)
+        eos = set(_eos_list(eos_token_id))
+        self.prepare_steps(max_new_tokens)
         self._row0 = torch.arange(B, device=dev, dtype=torch.int64) * self.cap
         self.hist = torch.zeros((B, max_new_tokens), dtype=torch.int64, device=dev)      # generated ids per sequence (the repetition penalty's set)
         self.nprev = torch.zeros(B, dtype=torch.int32, device=dev)
@@ -720,19 +731,7 @@ class BatchDecoder:
         self.cnt = torch.ones(1, dtype=torch.int64, device=dev)
         graph = None
         if use_graph and max_new_tokens > 2:
-            state = (self.tok, self.len, self.cnt, self.hist, self.nprev)
-            snap = tuple(t.clone() for t in state)
-            s = torch.cuda.Stream(device=dev)
-            s.wait_stream(torch.cuda.current_stream(dev))
-            with torch.cuda.stream(s):              # warm-up outside capture (workspaces, function attributes); undone below
-                self._graph_body(sp)
-            torch.cuda.current_stream(dev).wait_stream(s)
-            restore = lambda: [t.copy_(v) for t, v in zip(state, snap)]
-            restore()
-            graph = torch.cuda.CUDAGraph()
-            with _GEN_LOCK, torch.cuda.graph(graph, capture_error_mode="thread_local"):      # (_GEN_LOCK: see its definition)
-                self._graph_body(sp)
-            restore()
+            graph, _ = _capture_graph(dev, lambda: self._graph_body(sp), (self.tok, self.len, self.cnt, self.hist, self.nprev))
         steps = 1
         while steps < max_new_tokens:
             if graph is not None:
@@ -851,7 +850,7 @@ class LlavaQwenForCausalLM:
             if sp.repetition_penalty != 1.0:
                 raise NotImplementedError("beam search with a repetition penalty is not built")
             from .beam import beam_search
-            eos = self.eos_token_id if isinstance(self.eos_token_id, (list, tuple, set)) else ([] if self.eos_token_id is None else [self.eos_token_id])
+            eos = _eos_list(self.eos_token_id)
             dec = BatchDecoder(self.lm, [embeds[0]], max_new_tokens, replicate=int(num_beams))
             dec.prepare_steps(max_new_tokens)
 
@@ -862,7 +861,7 @@ class LlavaQwenForCausalLM:
             return torch.tensor([toks], dtype=torch.long, device=self.device)
         self.lm.reset_cache(max_seq=max(self.lm.max_seq, embeds.shape[1] + max_new_tokens))
         logits = self.lm.forward(embeds[0])
-        eos = self.eos_token_id if isinstance(self.eos_token_id, (list, tuple, set)) else ([] if self.eos_token_id is None else [self.eos_token_id])
+        eos = _eos_list(self.eos_token_id)
         seed = int(draw_seeds(1, generator if generator is not None else getattr(self, "seed_generator", None), kwargs.get("seed"))[0]) if sp.temperature > 0 else 0
         if max_new_tokens > 1 and generator is None and kwargs.get("decode_graph", True):
             # the token loop runs as a replayed hipGraph for greedy AND for sampling (token n draws counter_uniform(seed, n) inside the graph);

@@ -466,13 +466,10 @@ def assert_rows_close(inp, out, what=""):
 # ---------------------------------------------------------------- the case table ----------------------------------------------------------------
 
 def _prod_nsplit_trimmed(S):
-    """the split factor Qwen2Model.forward takes for its trimmed last layer, evaluated from that method's own source line"""
-    import inspect
-    import re
-    from streamchat_amd import llm as LM
-    m = re.search(r"^\s*nsplit = (.+)$", inspect.getsource(LM.Qwen2Model.forward), re.M)
-    assert m, "Qwen2Model.forward no longer computes `nsplit = ...` for its trimmed last layer"
-    return int(eval(m.group(1), {"S": S, "max": max, "min": min}))
+    """the split factor of the retired single-row trim of Qwen2Model.forward's last layer, which ran the final row alone through the causal
+    split-KV attention (~2 tiles of 64 keys per split, up to 128 splits).  No production call takes it any more; it is kept to size the
+    coverage of that kernel path (tests/test_host_logic.py pins the values)."""
+    return max(1, min(128, ((S + 63) // 64) // 2))
 
 
 def _prod_nsplit_batched(lens, Hq, Hkv, Dh):

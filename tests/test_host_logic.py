@@ -136,3 +136,13 @@ def test_conversation_templates_chatml():
     assert conv.get_prompt() == ("<|im_start|>system\nYou are a helpful assistant.<|im_end|>\n<|im_start|>user\n<image>\nwhat?<|im_end|>\n"
                                  "<|im_start|>assistant\n")
     assert conv_templates["qwen_1_5"].messages == []       # copy() does not alias
+
+
+def test_attention_case_table_split_factors():
+    """pins two split-KV factors of tests/_attn_cases.cases(): the retired single-row trim's, whose formula that module now holds itself,
+    and the batched rule's, which it takes from BatchDecoder.prepare_steps on a stub; and the table keeps its 26 cases"""
+    from tests import _attn_cases as A
+    table = {c.name: c.nsplit for c in A.cases()}
+    assert len(table) == 26
+    assert [table[f"trimmed last layer {S}"] for S in (65, 127, 128, 129, 8191, 49157)] == [1, 1, 1, 1, 64, 128]
+    assert table["batched caption decode"] == 25
