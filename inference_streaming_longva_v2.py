@@ -89,6 +89,11 @@ def parse_args(argv=None):
                    help="weights the batch-1 answer decode streams: fp8 = per-output-row OCP e4m3 copies of the projections and lm_head, half the "
                         "bytes per token (an accuracy trade, off by default: ~2.6 %% relative rms error per projection; +7.1 GB at 7B; prefill and "
                         "batched captions stay fp16).  A decoding setting like --temperature: not part of the memory fingerprint")
+    p.add_argument("--kv_cache", type=str, choices=["fp16", "fp8"], default="fp16",
+                   help="format of the batch-1 KV cache of every model of the process: fp8 = OCP e4m3 bytes with one power-of-two scale per (row, KV "
+                        "head, K or V), half the K/V bytes per decode token and 0.57 of the cache's memory (an accuracy trade, off by default: ~2.65 %% "
+                        "relative rms error per segment; head dim 128 only; batched captions and beam search keep fp16 caches).  A decoding setting like "
+                        "--decode_weights: not part of the memory fingerprint")
     args = p.parse_args(argv)
     if args.num_beams != 1 and (args.temperature or 0) > 0:
         # the reference forwards num_beams and do_sample = (temperature > 0) to HF generate (:252-256): with both that is HF's beam SAMPLING, which
@@ -130,6 +135,10 @@ def build_models(args):
     built = _build_models(args)
     if getattr(args, "decode_weights", "fp16") == "fp8":
         built[0].lm.enable_fp8_decode()
+    if getattr(args, "kv_cache", "fp16") == "fp8":
+        for m in built:
+            if isinstance(getattr(m, "lm", None), LM.Qwen2Model):
+                m.lm.set_kv_cache("fp8")
     return built
 
 

@@ -79,6 +79,15 @@ EXT_SIGNATURES = {
                                      c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p]),
 }
 
+# include/streamchat_hip_kv8.h - FP8 (e4m3) KV cache for batch-1 decode: a second additive extension header with a table of its own (base ABI 9
+# and both tables above are untouched); bound in load() like every other symbol
+KV8_SIGNATURES = {
+    "sc_kv8_quantize_rows": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p]),
+    "sc_kv8_dequantize_rows": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p]),
+    "sc_attention_kv8": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_float, c_int, c_void_p, c_int,
+                                 c_void_p, c_size_t, c_int, c_int, c_void_p]),
+}
+
 _lib = None
 
 
@@ -99,7 +108,7 @@ def load():
     except ImportError:
         pass
     lib = ctypes.CDLL(LIB_PATH)
-    for name, (res, args) in list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()):
+    for name, (res, args) in list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()) + list(KV8_SIGNATURES.items()):
         try:
             fn = getattr(lib, name)
         except AttributeError as e:

@@ -1,0 +1,377 @@
+// FP8 (OCP e4m3fn) KV cache for batch-1 decode (include/streamchat_hip_kv8.h): the row quantiser, its inverse, and k_attn_decode of
+// attention_decode.hip over e4m3 bytes.  A cache row is [K of all KV heads | V of all KV heads], 128 bytes per head, and every 128-element
+// segment has one power-of-two fp32 scale 2^e, e in [-14, 7]: code * 2^e is exact in fp16, so the attention kernel converts each operand to
+// exactly the fp16 value k_attn_decode reads from the dequantised cache and feeds the SAME fp16 MFMAs in the same order - its results are
+// bit-identical to that kernel's, the loop just streams half the bytes.  Default machine scheduler, as attention_decode.hip.
+#include "sc_common.h"
+#include "../../include/streamchat_hip_kv8.h"
+
+// attention_decode.hip: the split-KV merge, reused unchanged
+void sc_attn_combine_launch(int Dh, const float* part, void* out, int ldo, int B, int Sq, int Hq, int nsplit, int o_hs, long o_bs, hipStream_t s);
+
+namespace {
+
+typedef short sc_s4 __attribute__((ext_vector_type(4)));
+
+// LDS-DMA through a raw buffer resource: every lane's BYTES bytes land lane-linear behind `lds`; an offset at or past `extent` reads zeros
+__device__ __forceinline__ void lds_load16(const void* base, int extent, char* lds, unsigned voff) {
+    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, extent, 0x00020000);
+    __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (__attribute__((address_space(3))) void*)lds, 16, voff, 0, 0, 0);
+}
+__device__ __forceinline__ void lds_load4(const void* base, int extent, char* lds, unsigned voff) {
+    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, extent, 0x00020000);
+    __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (__attribute__((address_space(3))) void*)lds, 4, voff, 0, 0, 0);
+}
+
+// 8 e4m3 bytes -> 8 fp16 values code * s (s = a power of two as a packed fp16 pair: the product is exact, see the header)
+__device__ __forceinline__ sc_h8 cvt8(const sc_u2 w, const sc_h2 s) {
+    const sc_h2 a = __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(w[0], 1.0f, false) * s, b = __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(w[0], 1.0f, true) * s;
+    const sc_h2 c = __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(w[1], 1.0f, false) * s, d = __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(w[1], 1.0f, true) * s;
+    return sc_h8{a[0], a[1], b[0], b[1], c[0], c[1], d[0], d[1]};
+}
+
+// ------------------------------------------------------------------------------------------------------------------
+// Quantiser and its inverse: 16 lanes per 128-element segment, 8 elements per lane (one 16-byte load, one 8-byte store).
+// ------------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_kv8_quantize(const _Float16* __restrict__ x, int ld, int n, int nseg, uint8_t* __restrict__ cache, int cache_ld,
+                                                      float* __restrict__ scales, int cache_rows, int row0, const int* __restrict__ row0_dev, int x_follows) {
+    const int gid = blockIdx.x * 256 + threadIdx.x, seg = gid >> 4, l = gid & 15;
+    const int r0 = row0_dev ? row0_dev[0] : row0;
+    const int sg = seg < n * nseg ? seg : 0;                  // (lanes past the last segment redo segment 0 and store nothing)
+    const int i = sg / nseg, s = sg - i * nseg, row = r0 + i;
+    const bool live = seg < n * nseg && row >= 0 && row < cache_rows;
+    const int xr = x_follows ? (live ? row : 0) : i;
+    const sc_h8 v = *reinterpret_cast<const sc_h8*>(x + (size_t)xr * (size_t)ld + s * 128 + l * 8);
+    float m = 0.f;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) m = fmaxf(m, fabsf((float)v[e]));
+#pragma unroll
+    for (int sh = 8; sh >= 1; sh >>= 1) m = fmaxf(m, __shfl_xor(m, sh, 64));
+    // frexp(amax / 448) = (mant, e): amax / 448 is a normal fp32 for every non-zero fp16 amax, mant == 0.5 is a zero fraction field
+    const unsigned qb = __float_as_uint(__fdiv_rn(m, 448.f));
+    int e = (int)(qb >> 23) - 126 - ((qb & 0x7fffffu) == 0 ? 1 : 0);
+    e = m > 0.f ? min(max(e, -14), 7) : 0;
+    const float inv = __uint_as_float((unsigned)(127 - e) << 23);
+    float f[8];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) f[k] = fminf(fmaxf((float)v[k] * inv, -448.f), 448.f);      // x / 2^e is exact
+    int p0 = __builtin_amdgcn_cvt_pk_fp8_f32(f[0], f[1], 0, false), p1 = __builtin_amdgcn_cvt_pk_fp8_f32(f[4], f[5], 0, false);
+    p0 = __builtin_amdgcn_cvt_pk_fp8_f32(f[2], f[3], p0, true);
+    p1 = __builtin_amdgcn_cvt_pk_fp8_f32(f[6], f[7], p1, true);
+    if (live) {
+        *reinterpret_cast<sc_u2*>(cache + (size_t)row * (size_t)cache_ld + s * 128 + l * 8) = sc_u2{(unsigned)p0, (unsigned)p1};
+        if (l == 0) scales[(size_t)row * (size_t)nseg + s] = __uint_as_float((unsigned)(e + 127) << 23);
+    }
+}
+
+__global__ __launch_bounds__(256) void k_kv8_dequantize(const uint8_t* __restrict__ cache, int cache_ld, const float* __restrict__ scales, int row0, int n, int nseg,
+                                                        _Float16* __restrict__ out, int ld) {
+    const int gid = blockIdx.x * 256 + threadIdx.x, seg = gid >> 4, l = gid & 15;
+    if (seg >= n * nseg) return;
+    const int i = seg / nseg, s = seg - i * nseg;
+    const sc_u2 w = *reinterpret_cast<const sc_u2*>(cache + (size_t)(row0 + i) * (size_t)cache_ld + s * 128 + l * 8);
+    const _Float16 sh = (_Float16)scales[(size_t)(row0 + i) * (size_t)nseg + s];
+    *reinterpret_cast<sc_h8*>(out + (size_t)i * (size_t)ld + s * 128 + l * 8) = cvt8(w, sc_h2{sh, sh});
+}
+
+// ------------------------------------------------------------------------------------------------------------------
+// k_attn_decode (attention_decode.hip: 32-row chunks, the even chunk partition over splits and waves, one LDS-DMA ring per wave,
+// hand-counted vmcnt, the end-of-block merge) with e4m3 operands.  Per wave and ring stage:
+//   K bytes  4 KiB: rows of 128 B row-major, the 16-byte slot XORed with (row >> 1) & 7 on the SOURCE side, so the 8-byte A-fragment reads
+//            (ds_read_b64: bytes ds * 32 + g * 8 .. + 7 of row kvb * 16 + rl, the elements k_attn_decode's lane holds) of a half-wave
+//            cover 256 distinct bytes modulo the bank period;
+//   V bytes  4 KiB: rows of 128 B, unswizzled: pass i of the conversion reads 8 bytes per lane at i * 512 + lane * 8 (row i * 4 + lane / 16,
+//            piece lane % 16: ONE row, one scale per read);
+//   scales   256 B: ONE 4-byte DMA per chunk, lanes 0-31 the K scales of rows 0-31, lanes 32-63 the V scales in the order a lane reads
+//            them (slot w * 8 + i = row i * 4 + w);  it rides in front of the K bytes, so a chunk's scales are there with its K.
+// The converted V chunk (fp16(code * scale), 8 KiB, ONE per wave) is written in exactly k_attn_decode's V ring layout and read with its
+// ds_read_b64_tr_b16 reads; same-wave LDS write -> read needs an lgkmcnt wait and no barrier.  16.25 KiB per wave at DEC8_PD = 1.
+// Rows past the wave's range are outside the extent of ALL THREE buffer resources (bytes and scales): zeros, whatever memory holds there
+// (0 * 0 = 0 in the MFMA; a NaN scale or a NaN byte behind kv_len is never read).
+// vm queue of a wave:  [q x 4]  K(c0) V(c0) ..  then per chunk  K(c + PD)  V(c + PD);  K(c) = 1 scale op + 4 byte ops, V(c) = 4 ops.
+// ------------------------------------------------------------------------------------------------------------------
+constexpr int DCH = 32, DEC8_NW = 4, DEC8_NW_LOG = 2;
+#ifndef SC_DEC8_PD
+#define SC_DEC8_PD 1
+#endif
+constexpr int DEC8_PD = SC_DEC8_PD;
+constexpr int KB8 = DCH * 128, SCB = 256, VST = DCH * 256;                       // K or V bytes of a chunk, its scales, the fp16 V stage
+constexpr int WAVE_LDS8 = DEC8_PD * (2 * KB8 + SCB) + VST;
+
+__global__ __launch_bounds__(64 * DEC8_NW) void k_attn_kv8(const _Float16* __restrict__ Q, int ldq, const uint8_t* __restrict__ cache, int ldc,
+                                                           const float* __restrict__ scales, int Sq, int Skv, int Hkv, float scale_log2,
+                                                           const int* __restrict__ kv_len, float* __restrict__ part, int nsplit, int q_hs) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    constexpr int DH = 128, DS = 4, DB = 8, VROW = 256;
+    constexpr int CNT_K = 9 * DEC8_PD - 5, CNT_V = 9 * DEC8_PD - 4;                 // vm ops younger than K(c) / than V(c) at their waits
+    static_assert(DEC8_PD >= 1 && CNT_V < 64, "vmcnt is a 6-bit counter");
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int rl = lane & 15, g = lane >> 4;
+    const int split = blockIdx.x, h = blockIdx.y;
+    const int kv_valid = kv_len ? min(max(kv_len[0], 0), Skv) : Skv;
+    const int nch = (kv_valid + DCH - 1) / DCH;
+    const int cq = nch / nsplit, cr = nch - cq * nsplit;                                // the first cr splits take cq + 1 chunks
+    const int s_lo = split * cq + min(split, cr), ns = cq + (split < cr ? 1 : 0);
+    const int c_lo = s_lo + ((ns * wave) >> DEC8_NW_LOG), c_hi = s_lo + ((ns * (wave + 1)) >> DEC8_NW_LOG);
+    const int row_end = min(c_hi * DCH, kv_valid);                                      // rows of this wave: [c_lo * 32, row_end)
+
+    sc_u4 qf[DS];
+    {
+        const int qr = rl < Sq ? rl : Sq - 1;
+        const _Float16* qp = Q + (size_t)qr * (size_t)ldq + h * q_hs + g * 8;
+#pragma unroll
+        for (int ds = 0; ds < DS; ++ds) asm volatile("global_load_dwordx4 %0, %1, off offset:%2" : "=v"(qf[ds]) : "v"(qp), "n"(ds * 64) : "memory");
+    }
+    const int nseg = 2 * Hkv;
+    const uint8_t* kbase = cache + h * DH;
+    const uint8_t* vbase = cache + (Hkv + h) * DH;
+    const float* sbase = scales + h;
+    const bool any = c_lo < c_hi && row_end > 0;
+    const int b_ext = any ? (int)((unsigned)(row_end - 1) * (unsigned)ldc + DH) : 0;                       // K and V bytes (from kbase / vbase)
+    const int s_ext = any ? (int)(((unsigned)(row_end - 1) * (unsigned)nseg + (unsigned)Hkv + 1u) * 4u) : 0;   // scales (from sbase)
+    // per-lane source offsets inside a chunk.  16-byte granule j * 64 + lane lands at LDS byte (j * 64 + lane) * 16 = row j * 8 + (lane >> 3), slot lane & 7
+    unsigned k_vo[4], v_vo[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int r = j * 8 + (lane >> 3);
+        k_vo[j] = (unsigned)r * (unsigned)ldc + (unsigned)((((lane & 7) ^ ((r >> 1) & 7))) * 16);
+        v_vo[j] = (unsigned)r * (unsigned)ldc + (unsigned)((lane & 7) * 16);
+    }
+    const int sp = lane & 31, srow = lane < 32 ? sp : (sp & 7) * 4 + (sp >> 3);
+    const unsigned s_vo = ((unsigned)srow * (unsigned)nseg + (lane < 32 ? 0u : (unsigned)Hkv)) * 4u;
+    char* wbase = smem + wave * WAVE_LDS8;
+    char* kring = wbase;
+    char* vring = wbase + DEC8_PD * KB8;
+    char* sring = wbase + DEC8_PD * 2 * KB8;
+    const unsigned lds0 = (unsigned)(size_t)((__attribute__((address_space(3))) char*)smem) + (unsigned)(wave * WAVE_LDS8);
+    const unsigned k_lds = lds0, v_lds = lds0 + DEC8_PD * KB8, s_lds = lds0 + DEC8_PD * 2 * KB8, st_lds = lds0 + DEC8_PD * (2 * KB8 + SCB);
+    unsigned k_off[DS];
+#pragma unroll
+    for (int ds = 0; ds < DS; ++ds) k_off[ds] = (unsigned)(rl * 128 + (((ds * 2 + (g >> 1)) ^ ((rl >> 1) & 7)) << 4) + (g & 1) * 8);
+    // conversion pass i: row i * 4 + g, piece rl -> k_attn_decode's V ring slot piece ^ ((row & 7) << 1)
+    unsigned w_off[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) { const int r = i * 4 + g; w_off[i] = (unsigned)(r * VROW + ((rl ^ ((r & 7) << 1)) << 4)); }
+    const int vrow = 4 * g + (rl >> 2);
+    unsigned v_off[DB];
+#pragma unroll
+    for (int db = 0; db < DB; ++db) v_off[db] = (unsigned)(vrow * VROW + ((db ^ (vrow & 7)) << 5) + (rl & 3) * 8);
+
+    auto issue_k = [&](int c) {                                  // 1 + 4 LDS-DMA ops
+        const int st = c % DEC8_PD;
+        const bool in = c < c_hi;
+        lds_load4(sbase, in ? s_ext : 0, sring + st * SCB, (unsigned)c * (unsigned)(DCH * nseg * 4) + s_vo);
+        const unsigned ro = (unsigned)c * (unsigned)(DCH * ldc);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) lds_load16(kbase, in ? b_ext : 0, kring + st * KB8 + j * 1024, ro + k_vo[j]);
+    };
+    auto issue_v = [&](int c) {                                  // 4 LDS-DMA ops
+        const unsigned ro = (unsigned)c * (unsigned)(DCH * ldc);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) lds_load16(vbase, c < c_hi ? b_ext : 0, vring + (c % DEC8_PD) * KB8 + j * 1024, ro + v_vo[j]);
+    };
+
+    sc_f4 o[DB];
+#pragma unroll
+    for (int i = 0; i < DB; ++i) o[i] = sc_f4{0.f, 0.f, 0.f, 0.f};
+    float m_run = -INFINITY, l_run = 0.f;
+
+    if (any) {
+#pragma unroll
+        for (int u = 0; u < DEC8_PD; ++u) { issue_k(c_lo + u); issue_v(c_lo + u); }          // (past c_hi: zero extent -> no traffic)
+        for (int c = c_lo; c < c_hi; ++c) {
+            const unsigned st = (unsigned)(c % DEC8_PD);
+            // ---- S^T = K . Q^T for the 32 rows: K bytes, the chunk's scales ----
+            asm volatile("s_waitcnt vmcnt(%4)" : "+v"(qf[0]), "+v"(qf[1]), "+v"(qf[2]), "+v"(qf[3]) : "n"(CNT_K) : "memory");
+            sc_u2 kb[2][DS];
+            float ksc[2];
+            sc_f4 vsa, vsb;
+            const unsigned ka = k_lds + st * KB8, sa_ = s_lds + st * SCB;
+#pragma unroll
+            for (int ds = 0; ds < DS; ++ds) {
+                asm volatile("ds_read_b64 %0, %1" : "=v"(kb[0][ds]) : "v"(ka + k_off[ds]));
+                asm volatile("ds_read_b64 %0, %1 offset:%2" : "=v"(kb[1][ds]) : "v"(ka + k_off[ds]), "n"(16 * 128));
+            }
+            asm volatile("ds_read_b32 %0, %1" : "=v"(ksc[0]) : "v"(sa_ + rl * 4));
+            asm volatile("ds_read_b32 %0, %1 offset:64" : "=v"(ksc[1]) : "v"(sa_ + rl * 4));
+            asm volatile("ds_read_b128 %0, %1 offset:128" : "=v"(vsa) : "v"(sa_ + g * 32));
+            asm volatile("ds_read_b128 %0, %1 offset:144" : "=v"(vsb) : "v"(sa_ + g * 32));
+            asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(kb[0][0]), "+v"(kb[0][1]), "+v"(kb[0][2]), "+v"(kb[0][3]), "+v"(kb[1][0]), "+v"(kb[1][1]), "+v"(kb[1][2]),
+                                                  "+v"(kb[1][3]), "+v"(ksc[0]), "+v"(ksc[1]), "+v"(vsa), "+v"(vsb) :: "memory");
+            issue_k(c + DEC8_PD);                                  // K(c)'s stage and its scales are free: they are in registers
+            sc_f4 s[2];
+#pragma unroll
+            for (int kvb = 0; kvb < 2; ++kvb) {
+                const _Float16 kh = (_Float16)ksc[kvb];
+                const sc_h2 ks = {kh, kh};
+                s[kvb] = sc_f4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+                for (int ds = 0; ds < DS; ++ds)
+                    s[kvb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(cvt8(kb[kvb][ds], ks), __builtin_bit_cast(sc_h8, qf[ds]), s[kvb], 0, 0, 0);
+            }
+            // ---- exact online-softmax step (k_attn_decode's, instruction for instruction) ----
+            const int kv0 = c * DCH + g * 4;
+            float tmax = -INFINITY;
+#pragma unroll
+            for (int kvb = 0; kvb < 2; ++kvb)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    s[kvb][r] = (kv0 + kvb * 16 + r < row_end) ? s[kvb][r] : -INFINITY;
+                    tmax = fmaxf(tmax, s[kvb][r]);
+                }
+            const auto a = __builtin_amdgcn_permlane16_swap(__float_as_uint(tmax), __float_as_uint(tmax), false, false);
+            tmax = fmaxf(__uint_as_float(a[0]), __uint_as_float(a[1]));
+            const auto bsw = __builtin_amdgcn_permlane32_swap(__float_as_uint(tmax), __float_as_uint(tmax), false, false);
+            tmax = fmaxf(__uint_as_float(bsw[0]), __uint_as_float(bsw[1])) * scale_log2;
+            const float m_new = fmaxf(m_run, tmax);
+            const float m_use = (m_new == -INFINITY) ? 0.f : m_new;
+            const float alpha = __builtin_amdgcn_exp2f(m_run - m_use);
+            m_run = m_new;
+            l_run *= alpha;
+#pragma unroll
+            for (int db = 0; db < DB; ++db) o[db] *= alpha;
+            sc_h8 pf;
+            float ps = 0.f;
+#pragma unroll
+            for (int kvb = 0; kvb < 2; ++kvb)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const float p = __builtin_amdgcn_exp2f(__builtin_fmaf(s[kvb][r], scale_log2, -m_use));
+                    ps += p;
+                    pf[kvb * 4 + r] = (_Float16)p;
+                }
+            l_run += ps;
+            // ---- V(c) must have landed: bytes -> fp16(code * scale) -> the fp16 stage ----
+            asm volatile("s_waitcnt vmcnt(%0)" ::"n"(CNT_V) : "memory");
+            sc_u2 vb[8];
+            const unsigned va = v_lds + st * KB8 + (unsigned)lane * 8u;
+#pragma unroll
+            for (int i = 0; i < 8; ++i) asm volatile("ds_read_b64 %0, %1 offset:%2" : "=v"(vb[i]) : "v"(va), "n"(i * 512));
+            asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(vb[0]), "+v"(vb[1]), "+v"(vb[2]), "+v"(vb[3]), "+v"(vb[4]), "+v"(vb[5]), "+v"(vb[6]), "+v"(vb[7]) :: "memory");
+            issue_v(c + DEC8_PD);                                  // V(c)'s byte stage is free
+#pragma unroll
+            for (int i = 0; i < 8; ++i) {
+                const _Float16 vh = (_Float16)(i < 4 ? vsa[i & 3] : vsb[i & 3]);
+                const sc_u4 hv = __builtin_bit_cast(sc_u4, cvt8(vb[i], sc_h2{vh, vh}));
+                asm volatile("ds_write_b128 %0, %1" ::"v"(st_lds + w_off[i]), "v"(hv) : "memory");
+            }
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            // ---- O^T += V^T . P^T ----
+            sc_s4 lo[DB], hi[DB];
+#pragma unroll
+            for (int db = 0; db < DB; ++db) {
+                asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(lo[db]) : "v"(st_lds + v_off[db]) : "memory");
+                asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(hi[db]) : "v"(st_lds + v_off[db]), "n"(16 * VROW) : "memory");
+            }
+            asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(lo[0]), "+v"(hi[0]), "+v"(lo[1]), "+v"(hi[1]), "+v"(lo[2]), "+v"(hi[2]), "+v"(lo[3]), "+v"(hi[3]),
+                                                  "+v"(lo[4]), "+v"(hi[4]), "+v"(lo[5]), "+v"(hi[5]), "+v"(lo[6]), "+v"(hi[6]), "+v"(lo[7]), "+v"(hi[7]) :: "memory");
+#pragma unroll
+            for (int db = 0; db < DB; ++db) {
+                typedef short sc_s8 __attribute__((ext_vector_type(8)));
+                const sc_s8 v8 = {lo[db][0], lo[db][1], lo[db][2], lo[db][3], hi[db][0], hi[db][1], hi[db][2], hi[db][3]};
+                o[db] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(sc_h8, v8), pf, o[db], 0, 0, 0);
+            }
+        }
+    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");       // no LDS-DMA may still be in flight when the rings are reused / the block ends
+    // ---- merge the four waves of the split through LDS (aliases the rings: every wave is done with its own) ----
+    l_run += __shfl_xor(l_run, 16, 64);
+    l_run += __shfl_xor(l_run, 32, 64);
+    __syncthreads();
+    float* mo = reinterpret_cast<float*>(smem);             // [NW][DH][16] O^T, then [NW][16] m, [NW][16] l
+    float* mm = mo + DEC8_NW * DH * 16;
+    float* ml = mm + DEC8_NW * 16;
+#pragma unroll
+    for (int db = 0; db < DB; ++db)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) mo[(wave * DH + db * 16 + g * 4 + r) * 16 + rl] = o[db][r];
+    if (g == 0) { mm[wave * 16 + rl] = m_run; ml[wave * 16 + rl] = l_run; }
+    __syncthreads();
+    for (int e = tid; e < Sq * DH; e += 64 * DEC8_NW) {
+        const int q = e / DH, d = e - q * DH;
+        float M = mm[q];
+#pragma unroll
+        for (int w = 1; w < DEC8_NW; ++w) M = fmaxf(M, mm[w * 16 + q]);
+        float acc = 0.f, l = 0.f;
+#pragma unroll
+        for (int w = 0; w < DEC8_NW; ++w) {
+            const float mw = mm[w * 16 + q];
+            const float wt = (mw == -INFINITY) ? 0.f : __builtin_amdgcn_exp2f(mw - M);
+            acc += mo[(w * DH + d) * 16 + q] * wt;
+            l += ml[w * 16 + q] * wt;
+        }
+        float* pp = part + (((size_t)h * Sq + q) * nsplit + split) * (DH + 2);
+        pp[d] = acc;
+        if (d == 0) { pp[DH] = M; pp[DH + 1] = l; }
+    }
+}
+
+}  // namespace
+
+#define SC_KV8_DH(name)                                                                                                    \
+    do {                                                                                                                   \
+        if (Dh != 128) return sc_fail(SC_ERR_UNSUPPORTED, name ": head dim %d unsupported (the fp8 KV cache serves 128 only)", Dh); \
+    } while (0)
+
+extern "C" int sc_kv8_quantize_rows(const void* x, int ld, int n, int kv_heads, int Dh, uint8_t* cache, int cache_ld, float* scales, int cache_rows,
+                                    int row0, const int32_t* row0_dev, int x_follows_row, sc_stream_t stream) {
+    SC_REQUIRE(x && cache && scales, "sc_kv8_quantize_rows: null pointer argument");
+    SC_KV8_DH("sc_kv8_quantize_rows");
+    SC_REQUIRE(n > 0 && kv_heads > 0 && kv_heads <= 4096 && cache_rows > 0 && n <= cache_rows, "sc_kv8_quantize_rows: bad sizes (n, kv_heads, cache_rows positive, n <= cache_rows)");
+    const int w = 2 * kv_heads * Dh;
+    SC_REQUIRE(ld >= w && ld % 8 == 0 && cache_ld >= w && cache_ld % 8 == 0, "sc_kv8_quantize_rows: row strides must be multiples of 8, at least 2 * kv_heads * Dh");
+    SC_REQUIRE((reinterpret_cast<uintptr_t>(x) & 15) == 0 && (reinterpret_cast<uintptr_t>(cache) & 7) == 0, "sc_kv8_quantize_rows: x must be 16-byte aligned, cache 8-byte aligned");
+    SC_REQUIRE(row0_dev || (row0 >= 0 && row0 + n <= cache_rows), "sc_kv8_quantize_rows: rows row0 .. row0 + n - 1 exceed the cache");
+    const long segs = (long)n * 2 * kv_heads;
+    SC_REQUIRE(segs <= (1L << 27), "sc_kv8_quantize_rows: too many segments for one launch");
+    hipLaunchKernelGGL(k_kv8_quantize, dim3((unsigned)((segs + 15) / 16)), dim3(256), 0, (hipStream_t)stream, (const _Float16*)x, ld, n, 2 * kv_heads, cache, cache_ld,
+                       scales, cache_rows, row0, row0_dev, x_follows_row);
+    SC_CHECK_LAUNCH("sc_kv8_quantize_rows");
+    return SC_OK;
+}
+
+extern "C" int sc_kv8_dequantize_rows(const uint8_t* cache, int cache_ld, const float* scales, int cache_rows, int row0, int n, int kv_heads, int Dh,
+                                      void* out, int ld, sc_stream_t stream) {
+    SC_REQUIRE(cache && scales && out, "sc_kv8_dequantize_rows: null pointer argument");
+    SC_KV8_DH("sc_kv8_dequantize_rows");
+    SC_REQUIRE(n > 0 && kv_heads > 0 && kv_heads <= 4096 && cache_rows > 0, "sc_kv8_dequantize_rows: bad sizes (n, kv_heads, cache_rows positive)");
+    const int w = 2 * kv_heads * Dh;
+    SC_REQUIRE(ld >= w && ld % 8 == 0 && cache_ld >= w && cache_ld % 8 == 0, "sc_kv8_dequantize_rows: row strides must be multiples of 8, at least 2 * kv_heads * Dh");
+    SC_REQUIRE((reinterpret_cast<uintptr_t>(out) & 15) == 0 && (reinterpret_cast<uintptr_t>(cache) & 7) == 0, "sc_kv8_dequantize_rows: out must be 16-byte aligned, cache 8-byte aligned");
+    SC_REQUIRE(row0 >= 0 && n <= cache_rows && row0 <= cache_rows - n, "sc_kv8_dequantize_rows: rows row0 .. row0 + n - 1 exceed the cache");
+    const long segs = (long)n * 2 * kv_heads;
+    SC_REQUIRE(segs <= (1L << 27), "sc_kv8_dequantize_rows: too many segments for one launch");
+    hipLaunchKernelGGL(k_kv8_dequantize, dim3((unsigned)((segs + 15) / 16)), dim3(256), 0, (hipStream_t)stream, cache, cache_ld, scales, row0, n, 2 * kv_heads,
+                       (_Float16*)out, ld);
+    SC_CHECK_LAUNCH("sc_kv8_dequantize_rows");
+    return SC_OK;
+}
+
+extern "C" int sc_attention_kv8(const void* q, int ldq, const uint8_t* cache, int cache_ld, const float* scales, void* out, int ldo, int Sq, int Skv,
+                                int kv_heads, int Dh, float scale, int flags, const int32_t* kv_len, int nsplit, void* ws, size_t ws_bytes,
+                                int q_head_stride, int o_head_stride, sc_stream_t stream) {
+    SC_REQUIRE(q && cache && scales && out, "sc_attention_kv8: null pointer argument");
+    SC_KV8_DH("sc_attention_kv8");
+    SC_REQUIRE((flags & ~SC_ATTN_Q_PRESCALED) == 0, "sc_attention_kv8: flags must be 0 or SC_ATTN_Q_PRESCALED (the kernel is non-causal)");
+    SC_REQUIRE(Sq > 0 && Sq <= 16 && Skv > 0 && kv_heads > 0 && kv_heads <= 65535, "sc_attention_kv8: bad sizes (1 <= Sq <= 16 query rows per KV head)");
+    SC_REQUIRE(cache_ld >= 2 * kv_heads * Dh && cache_ld % 16 == 0 && (long)Skv * cache_ld < (1L << 31), "sc_attention_kv8: cache row stride must be a multiple of 16, at least 2 * kv_heads * Dh, the cache below 2 GiB");
+    SC_REQUIRE(ldq % 8 == 0 && ldo % 4 == 0, "sc_attention_kv8: leading dims must be multiples of 8 (out: 4)");
+    SC_REQUIRE(((reinterpret_cast<uintptr_t>(q) | reinterpret_cast<uintptr_t>(cache)) & 15) == 0 && (reinterpret_cast<uintptr_t>(scales) & 3) == 0 &&
+                   (reinterpret_cast<uintptr_t>(out) & 7) == 0, "sc_attention_kv8: q and cache must be 16-byte aligned, out 8-byte");
+    SC_REQUIRE(nsplit >= 1 && nsplit <= 1024, "sc_attention_kv8: nsplit must be in [1, 1024]");
+    const size_t need = (size_t)kv_heads * Sq * nsplit * (Dh + 2) * sizeof(float);
+    if (!ws || ws_bytes < need) return sc_fail(SC_ERR_WORKSPACE, "sc_attention_kv8: split-KV workspace %zu < required %zu", ws_bytes, need);
+    const int qhs = q_head_stride > 0 ? q_head_stride : Dh, ohs = o_head_stride > 0 ? o_head_stride : Dh;
+    SC_REQUIRE(qhs % 8 == 0 && ohs % 4 == 0, "sc_attention_kv8: head strides must be multiples of 8 (q) / 4 (out)");
+    hipStream_t s = (hipStream_t)stream;
+    const float sl2 = (flags & SC_ATTN_Q_PRESCALED) ? 1.0f : scale * 1.4426950408889634f;
+    constexpr int LDS_RING = DEC8_NW * WAVE_LDS8, LDS_MERGE = DEC8_NW * (128 * 16 + 32) * 4;
+    constexpr int LDS = LDS_RING > LDS_MERGE ? LDS_RING : LDS_MERGE;
+    sc_set_max_lds<k_attn_kv8>(LDS);
+    hipLaunchKernelGGL(k_attn_kv8, dim3((unsigned)nsplit, (unsigned)kv_heads), dim3(64 * DEC8_NW), LDS, s, (const _Float16*)q, ldq, cache, cache_ld, scales, Sq, Skv,
+                       kv_heads, sl2, kv_len, (float*)ws, nsplit, qhs);
+    sc_attn_combine_launch(128, (const float*)ws, out, ldo, 1, Sq, kv_heads, nsplit, ohs, (long)Sq * ldo, s);
+    SC_CHECK_LAUNCH("sc_attention_kv8");
+    return SC_OK;
+}

@@ -62,6 +62,19 @@ def check_decode_weights(v):
 DEFAULT_DECODE_WEIGHTS = check_decode_weights(os.environ.get("SC_DECODE_WEIGHTS") or "fp16")
 
 
+KV_CACHE = ("fp16", "fp8")
+
+
+def check_kv_cache(v):
+    if v not in KV_CACHE:
+        raise ValueError(f"kv_cache must be one of {KV_CACHE}, got {v!r}")
+    return v
+
+
+# SC_KV_CACHE=fp8: what Qwen2Model(kv_cache=None) means in this process (read once; the constructor argument wins)
+DEFAULT_KV_CACHE = check_kv_cache(os.environ.get("SC_KV_CACHE") or "fp16")
+
+
 # a layer's decode projections and, in Qwen2Model.w8["L"][l], the key of each one's per-row scales
 _W8_SCALES = dict(wq="sq", wkv="skv", wo="so", wgu="sgu", wd="sd")
 
@@ -79,8 +92,10 @@ def _h(t, device):
 class Qwen2Model:
     """Decoder stack + lm_head on the HIP kernels, with a contiguous per-layer KV cache [max_seq, 2*Hkv*Dh] (K | V)."""
 
-    def __init__(self, state_dict, cfg: Qwen2ConfigLite, device="cuda", max_seq=65536, consume=False, trim_last_layer=True, decode_weights=None):
+    def __init__(self, state_dict, cfg: Qwen2ConfigLite, device="cuda", max_seq=65536, consume=False, trim_last_layer=True, decode_weights=None, kv_cache=None):
         self.cfg, self.device, self.max_seq = cfg, torch.device(device), max_seq
+        self.kv_cache, self.kv8, self._kv_stage = "fp16", None, None
+        self.set_kv_cache(kv_cache if kv_cache is not None else DEFAULT_KV_CACHE)
         decode_weights = check_decode_weights(decode_weights if decode_weights is not None else DEFAULT_DECODE_WEIGHTS)
         self.w8 = None                              # enable_fp8_decode(): the e4m3 copies of the decode projections THIS object decodes from
         self._w8_shared = {}                        # ... which every shared_view() of these weights shares (quantised once, whoever asks first)
@@ -141,6 +156,27 @@ class Qwen2Model:
         self.w8 = self._w8_shared["w8"] = dict(L=layers, lm_head=head, slm_head=shead)
         return self
 
+    def set_kv_cache(self, mode):
+        """"fp8": the batch-1 KV cache of THIS object as OCP e4m3 bytes with one power-of-two scale per (row, KV head, K or V)
+        (include/streamchat_hip_kv8.h): half the K/V bytes per decode token and about 0.57 of the cache's footprint.  OPT-IN - an accuracy
+        trade, about 2.65 % relative rms error per segment; the kernels themselves are exact against the dequantised cache.  `self.kv8[l]` =
+        (bytes [max_seq, 2 Hkv Dh (+ pad)], scales [max_seq, 2 Hkv]); `self.cache[l]` is then, for EVERY layer, ONE fp16 staging buffer
+        [max_seq, 2 Hkv Dh (+ pad)]: the unchanged prefill and q/k/v kernels write fp16 rows into it and read the fp16 attention's operands from
+        it, and each layer moves its rows into its own fp8 cache before the next layer reuses the buffer.  Drops the cache this object holds.
+        A shared_view() inherits the mode and owns its cache; BatchDecoder keeps fp16 caches of its own.  Also: Qwen2Model(..., kv_cache="fp8"),
+        SC_KV_CACHE=fp8.
+
+        Invariant: while `kv_cache == "fp8"`, `cache[l] is _kv_stage` for every layer and `kv8` holds the rows.  forward() and the decode body
+        test the STRING only.  One place relies on that: BatchDecoder's per-sequence prefill lends the model its own fp16 caches and runs it
+        with the string set to "fp16" (plain assignment, saved and restored with `cache`), leaving `kv8` / `_kv_stage` where they are.  Calling
+        this method there instead would drop the fp8 cache."""
+        mode = check_kv_cache(mode)
+        if mode == "fp8" and self.cfg.head_dim != 128:
+            raise ValueError(f"kv_cache='fp8' needs head_dim 128, got {self.cfg.head_dim}")
+        if mode != self.kv_cache:
+            self.kv_cache, self.kv8, self._kv_stage, self.cache, self.cache_len, self._nsplit_prompt = mode, None, None, None, 0, None
+        return self
+
     def embed_tokens(self, ids):
         return ops.gather_rows(ids.to(self.device).view(-1), self.embed)
 
@@ -151,6 +187,7 @@ class Qwen2Model:
         import copy
         v = copy.copy(self)
         v.cache, v.cache_len, v._buf_rows, v._b, v._f32_scratch, v._nsplit_prompt = None, 0, 0, None, None, None
+        v.kv8, v._kv_stage = None, None
         v.max_seq = max_seq or self.max_seq
         return v
 
@@ -201,7 +238,14 @@ class Qwen2Model:
         if self.cache is None or self.cache[0].shape[0] < self.max_seq:
             # rows of [K of all KV heads | V of all KV heads]; KV_ROW_PAD extra halves per row (a view: every kernel takes the row stride)
             w = 2 * c.kv_heads * c.head_dim
-            self.cache = [torch.empty((self.max_seq, w + KV_ROW_PAD), dtype=torch.float16, device=self.device)[:, :w] for _ in range(c.layers)]
+            if self.kv_cache == "fp8":
+                # (the byte rows take the fp16 rows' pad in bytes: 2 * KV_ROW_PAD = 128 B by default)
+                e = lambda cols, dt: torch.empty((self.max_seq, cols), dtype=dt, device=self.device)
+                self.kv8 = [(e(w + 2 * KV_ROW_PAD, torch.uint8)[:, :w], e(2 * c.kv_heads, torch.float32)) for _ in range(c.layers)]
+                self._kv_stage = e(w + KV_ROW_PAD, torch.float16)[:, :w]
+                self.cache = [self._kv_stage] * c.layers
+            else:
+                self.cache = [torch.empty((self.max_seq, w + KV_ROW_PAD), dtype=torch.float16, device=self.device)[:, :w] for _ in range(c.layers)]
         self.cache_len = 0
         self._nsplit_prompt = None
 
@@ -230,8 +274,11 @@ class Qwen2Model:
         h.copy_(embeds)
         h2 = B["h2"][:n]
         S = pos0 + n
+        fp8 = self.kv_cache == "fp8"        # self.cache[l] is the fp16 staging buffer: see set_kv_cache
         for l, L in enumerate(self.L):
             x = ops.rmsnorm(h, L["ln1"], c.eps, out=B["x"][:n])
+            if fp8 and pos0 > 0:            # a chunk behind a non-empty cache: this layer's earlier rows back into the shared staging buffer
+                ops.kv8_dequantize_rows(*self.kv8[l], 0, pos0, c.kv_heads, Dh, self._kv_stage[:pos0])
             if self.trim_last_layer and last_only and l == len(self.L) - 1 and self._fused_ok(x, L, B["q"][:n], self.cache[l][pos0:S]):
                 # Only the last position's logits are wanted: in the LAST layer every row still contributes its K/V (cache), but nothing
                 # reads the query side of any row except the final one.  It runs for the rows b0.. of the attention q-block that holds the
@@ -254,11 +301,15 @@ class Qwen2Model:
                 xb = ops.rmsnorm(h2[b0:], L["ln2"], c.eps, out=B["x"][b0:n])
                 m = ops.gemm(xb, L["wgu"], None, epilogue="swiglu", out=B["m"][b0:n], dispatch_rows=n)
                 ops.gemm(m, L["wd"], None, residual=h2[b0:], out=h[b0:], dispatch_rows=n)
+                if fp8:
+                    ops.kv8_quantize_rows(self._kv_stage[pos0:S], *self.kv8[l], pos0, c.kv_heads, Dh)
                 break
             q, _ = self._qkv_rows(x, L, pos0, B["q"][:n], self.cache[l][pos0:S])      # K | V land in the cache rows; q pre-scaled
             ck = self.cache[l][:S]
             att = ops.attention(q.unsqueeze(0), ck[:, :dkv].unsqueeze(0), ck[:, dkv:].unsqueeze(0), c.heads, c.kv_heads, Dh, Dh ** -0.5,
                                 causal=True, out=B["att"][:n].unsqueeze(0), q_prescaled=True).squeeze(0)
+            if fp8:                         # the chunk's rows into this layer's fp8 cache, before the next layer reuses the staging buffer
+                ops.kv8_quantize_rows(self._kv_stage[pos0:S], *self.kv8[l], pos0, c.kv_heads, Dh)
             ops.gemm(att, L["wo"], None, residual=h, out=h2)
             x = ops.rmsnorm(h2, L["ln2"], c.eps, out=B["x"][:n])
             m = ops.gemm(x, L["wgu"], None, epilogue="swiglu", out=B["m"][:n])
@@ -287,6 +338,21 @@ class Qwen2Model:
         qv = q.as_strided((1, G, Dh), (dq, Dh, 1))
         return ops.attention(qv, ck[:, :dkv].unsqueeze(0), ck[:, dkv:].unsqueeze(0), c.kv_heads, c.kv_heads, Dh, Dh ** -0.5, causal=False,
                              kv_len=kv_len, nsplit=nsplit, q_head_stride=G * Dh, o_head_stride=G * Dh, out_ld=Dh, ws=ws, q_prescaled=True).view(1, dq)
+
+    def _decode_attend(self, l, q, rows, nsplit, row, kv_len=None, ws=None):
+        """attention of one token's q over layer l's cache rows [:rows] (None: the full capacity, `kv_len` of it valid).  fp16 cache:
+        _decode_attention.  fp8 cache: the q/k/v kernels left the token's k | v as fp16 in row `row` (host int, or device int32 in a captured
+        step) of the staging buffer; it is quantised into the layer's cache first and attended from its quantised form (attention_kv8)."""
+        if self.kv_cache != "fp8":
+            return self._decode_attention(q, self.cache[l] if rows is None else self.cache[l][:rows], nsplit, kv_len=kv_len, ws=ws)
+        c = self.cfg
+        dq, Dh, G = c.heads * c.head_dim, c.head_dim, c.heads // c.kv_heads
+        kb, ks = self.kv8[l]
+        ops.kv8_quantize_rows(self._kv_stage, kb, ks, row, c.kv_heads, Dh, x_follows_row=True)
+        if rows is not None:
+            kb, ks = kb[:rows], ks[:rows]
+        return ops.attention_kv8(q.as_strided((1, G, Dh), (dq, Dh, 1)), kb, ks, c.kv_heads, Dh, Dh ** -0.5, kv_len=kv_len, nsplit=nsplit,
+                                 q_head_stride=G * Dh, o_head_stride=G * Dh, out_ld=Dh, ws=ws, q_prescaled=True).view(1, dq)
 
     def _decode_tail(self, l, P, h, att):
         """o projection + residual, gate/up with the fused RMSNorm and SwiGLU, down projection + residual -> the layer's output [1, H]"""
@@ -317,7 +383,7 @@ class Qwen2Model:
             kv32 = _gemv(P["wkv"], h, L["bkv"], out_f32=True, rms_gamma=L["ln1"], rms_eps=c.eps).view(1, 2 * dkv)
             q = ops.rope_f32in(q32, tq, c.heads, Dh, torch.empty((1, dq), dtype=torch.float16, device=self.device), 0, pos0)
             ops.rope_f32in(kv32, tk, c.kv_heads, Dh, self.cache[l][pos0:S], dkv, pos0)
-            h = self._decode_tail(l, P, h, self._decode_attention(q, self.cache[l][:S], nsplit))
+            h = self._decode_tail(l, P, h, self._decode_attend(l, q, S, nsplit, pos0))
         self.cache_len = S
         return self._decode_logits(h)
 
@@ -531,7 +597,8 @@ class DecodeGraph:
         self._captured_ptrs = None
 
     def _ptrs(self):
-        return tuple(c.data_ptr() for c in self.lm.cache) + (self.lm.cache[0].shape[0], self.tab_q.data_ptr(), self.tab_k.data_ptr())
+        kv8 = tuple(t.data_ptr() for pair in (self.lm.kv8 or ()) for t in pair)          # (the fp8 cache's bytes and scales, when there is one)
+        return tuple(c.data_ptr() for c in self.lm.cache) + kv8 + (self.lm.cache[0].shape[0], self.tab_q.data_ptr(), self.tab_k.data_ptr())
 
     def valid(self):
         """False once the KV cache was reallocated after capture (reset_cache with a larger max_seq): the graph would replay into
@@ -548,7 +615,7 @@ class DecodeGraph:
             (wq, sq), (wkv, skv) = P["wq"], P["wkv"]
             rest = (L["bq"], L["bkv"], h, L["ln1"], c.eps, self.q_buf, lm.cache[l], self.pos, c.heads, c.kv_heads, c.head_dim, self.tab_q, self.tab_k)
             q = (ops.decode_qkv_tab(wq, wkv, *rest) if sq is None else ops.decode_qkv_tab_w8(wq, sq, wkv, skv, *rest)).view(1, dq)
-            h = lm._decode_tail(l, P, h, lm._decode_attention(q, lm.cache[l], self.nsplit, kv_len=self.len, ws=self.ws_attn))
+            h = lm._decode_tail(l, P, h, lm._decode_attend(l, q, None, self.nsplit, self.pos, kv_len=self.len, ws=self.ws_attn))
         logits = lm._decode_logits(h)
         sp = self.sampling                                                   # HIP next-token kernels over the 152 064 logits (sampling.hip)
         u = ops.counter_uniform(self.seed, self.cnt, 1, out=self.u) if sp.temperature > 0 else None      # token n = cnt + 1 (the first was picked by the caller)
@@ -630,14 +697,17 @@ class BatchDecoder:
         first_logits = []
         # (forward() also records the split-KV factor of "the prompt in the cache": it belongs to the saved state - ADVICE r04 - or an eager
         #  decode that continues the earlier prompt would merge its partials in another grouping than a DecodeGraph built for it)
-        saved = (lm.cache, lm.cache_len, lm.max_seq, lm._nsplit_prompt)
+        # (the per-sequence prefill below writes THIS object's fp16 caches: on an fp8-cache model it runs in fp16 mode.  The mode STRING is
+        #  assigned, not set_kv_cache(): that would drop lm.kv8 - see the invariant in its docstring)
+        saved = (lm.cache, lm.cache_len, lm.max_seq, lm._nsplit_prompt, lm.kv_cache)
         try:
+            lm.kv_cache = "fp16"
             for b, e in enumerate(prompts):
                 lm.cache, lm.cache_len, lm.max_seq = [cl[b] for cl in self.cache], 0, self.cap
                 first_logits.append(lm.forward(e.to(dev)))
                 self.len[b] = lm.cache_len
         finally:
-            lm.cache, lm.cache_len, lm.max_seq, lm._nsplit_prompt = saved
+            lm.cache, lm.cache_len, lm.max_seq, lm._nsplit_prompt, lm.kv_cache = saved
         if replicate is not None:                      # slot 0 holds the prompt: the other beams get its K / V rows and its logits
             n0 = int(self.len[0].item())
             for cl in self.cache:

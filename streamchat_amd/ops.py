@@ -825,6 +825,74 @@ def decode_qkv_tab_w8(wq, sq, wkv, skv, bq, bkv, x, rms_gamma, rms_eps: float, q
     return q_out
 
 
+def _kv8_operands(cache, scales, kv_heads, Dh, what):
+    if (cache.dtype != torch.uint8 or scales.dtype != torch.float32 or cache.dim() != 2 or cache.stride(1) != 1 or cache.shape[1] != 2 * kv_heads * Dh
+            or not scales.is_contiguous() or scales.shape != (cache.shape[0], 2 * kv_heads)):
+        raise StreamChatHipError(f"{what}: the cache must be e4m3 bytes (uint8 [rows, 2 * kv_heads * Dh], unit column stride) with fp32 scales [rows, 2 * kv_heads]")
+
+
+def kv8_quantize_rows(x, cache, scales, row0, kv_heads: int, Dh: int, x_follows_row: bool = False):
+    """fp16 rows x [n, 2 * kv_heads * Dh] (K | V of every KV head; rows may be strided) -> e4m3 bytes and power-of-two scales of the cache rows
+    row0 .. row0 + n - 1 (include/streamchat_hip_kv8.h; tests/_kv8.py is the specification).  `row0`: a host int, or an int32 device tensor (a
+    captured decode step).  x_follows_row: x is laid out row for row like the cache and n = 1 rows are taken from x[row0 ..]; pass the whole
+    buffer.  Writes those rows' bytes and scales and nothing else."""
+    _require_cuda(x, cache, scales)
+    _kv8_operands(cache, scales, kv_heads, Dh, "kv8_quantize_rows")
+    if x.dtype != torch.float16 or x.dim() != 2 or x.stride(1) != 1 or x.shape[1] != 2 * kv_heads * Dh:
+        raise StreamChatHipError("kv8_quantize_rows: fp16 [n, 2 * kv_heads * Dh] with unit column stride")
+    dev_row = isinstance(row0, torch.Tensor)
+    if dev_row:
+        _require_cuda(row0)
+        if row0.dtype != torch.int32:
+            raise StreamChatHipError("kv8_quantize_rows: a device-resident row0 must be int32")
+    n = 1 if x_follows_row else x.shape[0]
+    from ctypes import c_void_p
+    with torch.cuda.device(x.device), _timed("k_kv8_quantize", 0.0):
+        check(_lib.load().sc_kv8_quantize_rows(c_void_p(x.data_ptr()), x.stride(0), n, kv_heads, Dh, c_void_p(cache.data_ptr()), cache.stride(0), ptr(scales),
+                                               cache.shape[0], 0 if dev_row else int(row0), ptr(row0) if dev_row else None, 1 if x_follows_row else 0,
+                                               stream_ptr(x.device)), "sc_kv8_quantize_rows")
+
+
+def kv8_dequantize_rows(cache, scales, row0: int, n: int, kv_heads: int, Dh: int, out):
+    """out[i] (fp16 [n, 2 * kv_heads * Dh], rows may be strided) = code * scale of cache row row0 + i, exact"""
+    _require_cuda(cache, scales, out)
+    _kv8_operands(cache, scales, kv_heads, Dh, "kv8_dequantize_rows")
+    if out.dtype != torch.float16 or out.dim() != 2 or out.stride(1) != 1 or out.shape != (n, 2 * kv_heads * Dh):
+        raise StreamChatHipError("kv8_dequantize_rows: out must be fp16 [n, 2 * kv_heads * Dh] with unit column stride")
+    from ctypes import c_void_p
+    with torch.cuda.device(out.device), _timed("k_kv8_dequantize", 0.0):
+        check(_lib.load().sc_kv8_dequantize_rows(c_void_p(cache.data_ptr()), cache.stride(0), ptr(scales), cache.shape[0], int(row0), int(n), kv_heads, Dh,
+                                                 c_void_p(out.data_ptr()), out.stride(0), stream_ptr(out.device)), "sc_kv8_dequantize_rows")
+    return out
+
+
+def attention_kv8(q, cache, scales, kv_heads: int, Dh: int, scale: float, kv_len=None, out=None, nsplit: int = 1, q_head_stride: int = 0,
+                  o_head_stride: int = 0, out_ld=None, ws=None, q_prescaled: bool = False):
+    """`attention` of a decode step (q [1, Sq <= 16, *]: Sq query rows per KV head, non-causal, split-KV) over an e4m3 cache [Skv, 2 * kv_heads * Dh]
+    with its scales (kv8_quantize_rows).  Bit-identical to `attention` with the same nsplit over the dequantised cache.  Returns [1, Sq, kv_heads * Dh]."""
+    _require_cuda(q, cache, scales)
+    _kv8_operands(cache, scales, kv_heads, Dh, "attention_kv8")
+    if q.dtype != torch.float16 or q.dim() != 3 or q.shape[0] != 1 or q.stride(-1) != 1:
+        raise StreamChatHipError("attention_kv8: q must be fp16 [1, Sq, *] with unit last stride")
+    Sq, Skv = q.shape[1], cache.shape[0]
+    if out is None:
+        out = torch.empty((1, Sq, kv_heads * Dh), dtype=torch.float16, device=q.device)
+    from ctypes import c_void_p
+    P = lambda t: None if t is None else c_void_p(t.data_ptr())
+    ldo = out.stride(1) if out_ld is None else out_ld
+    kl = None if kv_len is None else kv_len.to(device=q.device, dtype=torch.int32).contiguous()
+    need = kv_heads * Sq * nsplit * (Dh + 2) * 4
+    if ws is None:
+        ws = _workspace(need, q.device)
+    elif ws.numel() * ws.element_size() < need:
+        raise StreamChatHipError(f"attention_kv8: workspace {ws.numel() * ws.element_size()} < required {need}")
+    with torch.cuda.device(q.device), _timed("k_attn_kv8", 4.0 * kv_heads * Sq * Skv * Dh):
+        check(_lib.load().sc_attention_kv8(P(q), q.stride(1), P(cache), cache.stride(0), P(scales), P(out), ldo, Sq, Skv, kv_heads, Dh, c_float(scale),
+                                           2 if q_prescaled else 0, P(kl), nsplit, P(ws), c_size_t(ws.numel() * ws.element_size()), q_head_stride, o_head_stride,
+                                           stream_ptr(q.device)), "sc_attention_kv8")
+    return out
+
+
 def decode_advance(nxt, ring, cnt, tok, pos, kv_len, nprev):
     """one launch: ring[cnt] = nxt; tok = nxt; cnt, pos, kv_len, nprev += 1 (device scalars of a captured decode step)"""
     _require_cuda(nxt, ring, cnt, tok, pos, kv_len, nprev)
