@@ -18,7 +18,7 @@
 // bank-conflict-free XOR swizzles on the per-lane source address and on the reads.  The KV loop is a general tile body plus a
 // steady-state loop with no mask, no row max and no O rescale (see the notes at the loop); what bounds it - LDS fragment
 // traffic and the SIMD issue port - is measured in tools/probes/ and summarised in DESIGN.md section 4.
-#include "sc_common.h"
+#include "attention_decode_common.h"                   // lds_load16, sc_s4
 #include <type_traits>
 
 // attention_decode.hip (its own translation unit: default machine scheduler)
@@ -30,18 +30,9 @@ namespace {
 
 typedef __attribute__((address_space(3))) void* lds_ptr_t;
 typedef const __attribute__((address_space(1))) void* glb_ptr_t;
-typedef short sc_s4 __attribute__((ext_vector_type(4)));
 typedef float sc_f2 __attribute__((ext_vector_type(2)));
 
 constexpr int KVT = 64;   // kv rows per tile
-
-// 16-byte LDS-DMA through a raw buffer resource (base, extent in bytes): lane address = base + voff + soff, destination = the
-// wave-uniform LDS pointer + lane * 16; out-of-range lanes write zeros.  A free function because an opaque
-// __amdgpu_buffer_rsrc_t inside a lambda of the kernel silently drops the kernel's host stub.
-__device__ __forceinline__ void lds_load16(const void* base, int extent, char* lds, unsigned voff, int soff) {
-    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, extent, 0x00020000);
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (__attribute__((address_space(3))) void*)lds, 16, voff, soff, 0, 0);
-}
 
 // PRE (SC_ATTN_Q_PRESCALED): the caller's Q already carries the softmax scale in the log2 domain (q * scale * log2 e, applied by the
 // PRODUCER of q to its fp32 accumulators before the one rounding to fp16: the rotary / column-scale epilogues of gemm.hip, k_decode_qkv,

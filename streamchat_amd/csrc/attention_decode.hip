@@ -2,17 +2,9 @@
 // the split-KV merge k_attn_combine and the per-wave streaming kernel k_attn_decode.  A translation unit of their own because
 // attention.hip is built with hipcc's iterative-ILP machine scheduler (good for the MFMA-bound tile kernel: +3 % on the 49 k prefill),
 // which costs these HBM-bound kernels 0.6-2 % (profiles/r03_run49_51_attn_sched_strategy.md): this file takes the default scheduler.
-#include "sc_common.h"
+#include "attention_decode_common.h"
 
 namespace {
-
-typedef short sc_s4 __attribute__((ext_vector_type(4)));
-
-// 16-byte LDS-DMA through a raw buffer resource (see attention.hip)
-__device__ __forceinline__ void lds_load16(const void* base, int extent, char* lds, unsigned voff, int soff) {
-    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, extent, 0x00020000);
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (__attribute__((address_space(3))) void*)lds, 16, voff, soff, 0, 0);
-}
 
 // merge of the split-KV partials: out = sum_i O_i 2^(m_i - M) / sum_i l_i 2^(m_i - M).  One workgroup (DH threads) per
 // (batch, head, query): the split weights are computed once by the first wave (one lane per split), then every thread owns one
@@ -91,11 +83,9 @@ __global__ void k_attn_combine(const float* __restrict__ part, _Float16* __restr
 //   rows past the wave's range are outside the buffer resource's extent: zeros, no memory traffic (the row part of every address
 //   stays in the VGPR offset, which is what the range check covers).
 // The MFMA operands are element for element those of the round-3 kernel: results are bit-identical to it.
-// Exact online softmax per chunk (the loop is bandwidth-bound, the VALU work is free).  The four waves of a workgroup cover four
-// consecutive quarters of one split; they merge their (O, m, l) through LDS at the end, so a workgroup leaves ONE partial per split
-// in the layout k_attn_combine reads.
+// The chunk partition, the Q fragments, the online-softmax step, the V^T reads, the P.V MFMAs and the merge of the workgroup's waves into ONE
+// partial per split are attention_decode_common.h's, shared with k_attn_kv8 (attention_kv8.hip); the reasons are written there.
 // ------------------------------------------------------------------------------------------------------------------
-constexpr int DCH = 32;                            // kv rows per chunk
 // Diagnostic build only (-DSC_DEC_TRACE, tools/trace_decode_attn.py): five 100-MHz wall-clock stamps per wave of the LAST launch
 #ifdef SC_DEC_TRACE
 __device__ unsigned long long sc_dec_trace_buf[8192 * 8];
@@ -103,14 +93,6 @@ __device__ unsigned long long sc_dec_trace_buf[8192 * 8];
 #else
 #define DEC_STAMP(i) do { } while (0)
 #endif
-#ifndef SC_DEC_ABL
-#define SC_DEC_ABL 0
-#endif
-#ifndef SC_DEC_NW
-#define SC_DEC_NW 4                                // streaming waves per workgroup (a power of two)
-#endif
-constexpr int DEC_NW = SC_DEC_NW, DEC_NW_LOG = DEC_NW == 8 ? 3 : (DEC_NW == 4 ? 2 : (DEC_NW == 2 ? 1 : 0));
-static_assert((1 << DEC_NW_LOG) == DEC_NW, "1, 2, 4 or 8 waves");
 
 // DEC_PD = chunks in flight per wave = stages of the K and of the V ring: ONE (64 KiB of LDS per workgroup, two workgroups per CU).
 // Measured on the same box at a 49 k context 326.2 tokens/s against 323.7 with two stages (128 KiB, one workgroup per CU; 64 splits;
@@ -125,7 +107,7 @@ __global__ __launch_bounds__(64 * DEC_NW) void k_attn_decode(const _Float16* __r
     extern __shared__ __attribute__((aligned(16))) char smem[];
     static_assert(DH == 128, "the K ring is laid out for 256-byte rows");
     static_assert(DEC_PD >= 1 && 16 * DEC_PD - 8 < 64, "vmcnt is a 6-bit counter");
-    constexpr int DS = DH / 32, DB = DH / 16, VROW = DH * 2, CHB = DCH * VROW;          // bytes of one K or V chunk (8 KiB at Dh = 128)
+    constexpr int DS = DH / 32, DB = DH / 16, VROW = DEC_VROW, CHB = DCH * VROW;        // bytes of one K or V chunk (8 KiB at Dh = 128)
     constexpr int WAVE_LDS = 2 * DEC_PD * CHB;                                          // [K stages | V stages] of one wave
     constexpr int CNT = 16 * DEC_PD - 8;                                                // vm ops younger than the chunk part being waited for (see the loop)
     const int tid = threadIdx.x, lane = tid & 63;
@@ -133,11 +115,7 @@ __global__ __launch_bounds__(64 * DEC_NW) void k_attn_decode(const _Float16* __r
     const int rl = lane & 15, g = lane >> 4;
     // grid = (split, head, batch): no integer division in the prologue (round 4 decoded a flat block index with three of them, ~60
     // scalar instructions in front of the first memory request of a 22 us kernel)
-#ifdef SC_DEC_HROT          // diagnostic: which head a grid row works on (does a slow row follow the grid position or the head's addresses?)
-    const int split = blockIdx.x, h = (blockIdx.y + SC_DEC_HROT) % gridDim.y, b = blockIdx.z;
-#else
     const int split = blockIdx.x, h = blockIdx.y, b = blockIdx.z;
-#endif
     DEC_STAMP(0);
 #ifdef SC_DEC_TRACE
     {   // where this wave runs: HW_ID (cu_id [11:8], sh_id [12], se_id [15:13]) and the XCC id
@@ -149,31 +127,10 @@ __global__ __launch_bounds__(64 * DEC_NW) void k_attn_decode(const _Float16* __r
 #endif
     const int hk = group == 1 ? h : h / group;                                          // group = Hq / Hkv (1 when the caller packs the G heads as query rows)
     const int kv_valid = kv_len ? min(kv_len[b], Skv) : Skv;
-    // chunks of this split, then of this wave: EVEN shares (sizes differ by at most one chunk).  Round 4 cut ceil(nch / nsplit) chunks per
-    // split and ceil(that / 4) per wave: at 49 153 keys (1537 chunks, 64 splits) that is 25 chunks for 61 workgroups, 12 for one and none
-    // for two, and 7 | 7 | 7 | 4 inside a workgroup - the launch lasted 7 chunk times where 6.004 would do
-#ifdef SC_DEC_OLD_PARTITION
-    const int cps = ((kv_valid + DCH - 1) / DCH + nsplit - 1) / nsplit, nch = (kv_valid + DCH - 1) / DCH;
-    const int s_lo = min(split * cps, nch), s_hi = min(s_lo + cps, nch);
-    const int cpw = (s_hi - s_lo + DEC_NW - 1) >> DEC_NW_LOG;
-    const int c_lo = min(s_lo + wave * cpw, s_hi), c_hi = min(c_lo + cpw, s_hi);
-#else
-    const int nch = (kv_valid + DCH - 1) / DCH;
-    const int cq = nch / nsplit, cr = nch - cq * nsplit;                                // the first cr splits take cq + 1 chunks
-    const int s_lo = split * cq + min(split, cr), ns = cq + (split < cr ? 1 : 0);
-    const int c_lo = s_lo + ((ns * wave) >> DEC_NW_LOG), c_hi = s_lo + ((ns * (wave + 1)) >> DEC_NW_LOG);
-#endif
-    const int row_end = min(c_hi * DCH, kv_valid);                                      // rows of this wave: [c_lo * 32, row_end)
-
-    // Q fragments (B operand: column = query row rl, k-slots = 8 head-dim elements): inline asm, so that no compiler-tracked vector
-    // load is pending when the DMA queue starts (see the header); waited for together with the first K chunk
+    const DecRange wr = dec_range<DEC_NW_LOG>(kv_valid, nsplit, split, wave);
+    const int c_lo = wr.c_lo, c_hi = wr.c_hi, row_end = wr.row_end;                     // (plain ints: the issue lambdas capture them)
     sc_u4 qf[DS];
-    {
-        const int qr = rl < Sq ? rl : Sq - 1;
-        const _Float16* qp = Q + (size_t)b * (size_t)q_bs + (size_t)qr * (size_t)ldq + h * q_hs + g * 8;
-#pragma unroll
-        for (int ds = 0; ds < DS; ++ds) asm volatile("global_load_dwordx4 %0, %1, off offset:%2" : "=v"(qf[ds]) : "v"(qp), "n"(ds * 64) : "memory");
-    }
+    dec_load_q(Q + (size_t)b * (size_t)q_bs + h * q_hs, ldq, Sq, rl, g, qf);
     const _Float16* kbase = Kp + (size_t)b * Skv * (size_t)ldk + hk * DH;
     const _Float16* vbase = Vp + (size_t)b * Skv * (size_t)ldv + hk * DH;
     const bool any = c_lo < c_hi;
@@ -196,22 +153,20 @@ __global__ __launch_bounds__(64 * DEC_NW) void k_attn_decode(const _Float16* __r
     unsigned k_off[DS];
 #pragma unroll
     for (int ds = 0; ds < DS; ++ds) k_off[ds] = (unsigned)(rl * VROW + (((ds * 4 + g) ^ rl) << 4));
-    const int vrow = 4 * g + (rl >> 2);
     unsigned v_off[DB];
-#pragma unroll
-    for (int db = 0; db < DB; ++db) v_off[db] = (unsigned)(vrow * VROW + ((db ^ (vrow & 7)) << 5) + (rl & 3) * 8);
+    dec_v_offsets(rl, g, v_off);
 
     auto issue_k = [&](int c) {                                  // 8 LDS-DMA ops
         const unsigned ro = (unsigned)c * (unsigned)(DCH * ldk * 2);
         char* dst = kring + (c % DEC_PD) * CHB;
 #pragma unroll
-        for (int j = 0; j < 8; ++j) lds_load16(kbase, c < c_hi ? k_ext : 0, dst + j * 1024, ro + k_vo[j], 0);
+        for (int j = 0; j < 8; ++j) lds_load16(kbase, c < c_hi ? k_ext : 0, dst + j * 1024, ro + k_vo[j]);
     };
     auto issue_v = [&](int c) {                                  // 8 LDS-DMA ops
         const unsigned ro = (unsigned)c * (unsigned)(DCH * ldv * 2);
         char* dst = vring + (c % DEC_PD) * CHB;
 #pragma unroll
-        for (int j = 0; j < 8; ++j) lds_load16(vbase, c < c_hi ? v_ext : 0, dst + j * 1024, ro + v_vo[j], 0);
+        for (int j = 0; j < 8; ++j) lds_load16(vbase, c < c_hi ? v_ext : 0, dst + j * 1024, ro + v_vo[j]);
     };
 
     sc_f4 o[DB];
@@ -228,13 +183,6 @@ __global__ __launch_bounds__(64 * DEC_NW) void k_attn_decode(const _Float16* __r
         DEC_STAMP(1);
         for (int c = c_lo; c < c_hi; ++c) {
             const unsigned stage = (unsigned)((c % DEC_PD) * CHB);
-#if SC_DEC_ABL == 1                 // ablation: the stream alone (waits + re-issue, no LDS reads, no arithmetic)
-            asm volatile("s_waitcnt vmcnt(%0)" ::"n"(CNT) : "memory");
-            issue_k(c + DEC_PD);
-            asm volatile("s_waitcnt vmcnt(%0)" ::"n"(CNT) : "memory");
-            issue_v(c + DEC_PD);
-            continue;
-#endif
             // ---- S^T = K . Q^T for the 32 rows ----
             static_assert(DS == 4, "the fences below name 8 K fragments and 4 q fragments");
             asm volatile("s_waitcnt vmcnt(%4)" : "+v"(qf[0]), "+v"(qf[1]), "+v"(qf[2]), "+v"(qf[3]) : "n"(CNT) : "memory");
@@ -257,91 +205,18 @@ __global__ __launch_bounds__(64 * DEC_NW) void k_attn_decode(const _Float16* __r
                 for (int ds = 0; ds < DS; ++ds)
                     s[kvb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(sc_h8, kf[kvb][ds]), __builtin_bit_cast(sc_h8, qf[ds]), s[kvb], 0, 0, 0);
             }
-            // ---- exact online-softmax step ----
-            const int kv0 = c * DCH + g * 4;
-            float tmax = -INFINITY;
-#pragma unroll
-            for (int kvb = 0; kvb < 2; ++kvb)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    s[kvb][r] = (kv0 + kvb * 16 + r < row_end) ? s[kvb][r] : -INFINITY;
-                    tmax = fmaxf(tmax, s[kvb][r]);
-                }
-            const auto a = __builtin_amdgcn_permlane16_swap(__float_as_uint(tmax), __float_as_uint(tmax), false, false);
-            tmax = fmaxf(__uint_as_float(a[0]), __uint_as_float(a[1]));
-            const auto bsw = __builtin_amdgcn_permlane32_swap(__float_as_uint(tmax), __float_as_uint(tmax), false, false);
-            tmax = fmaxf(__uint_as_float(bsw[0]), __uint_as_float(bsw[1])) * scale_log2;
-            const float m_new = fmaxf(m_run, tmax);
-            const float m_use = (m_new == -INFINITY) ? 0.f : m_new;
-            const float alpha = __builtin_amdgcn_exp2f(m_run - m_use);
-            m_run = m_new;
-            l_run *= alpha;
-#pragma unroll
-            for (int db = 0; db < DB; ++db) o[db] *= alpha;
-            sc_h8 pf;
-            float ps = 0.f;
-#pragma unroll
-            for (int kvb = 0; kvb < 2; ++kvb)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const float p = __builtin_amdgcn_exp2f(__builtin_fmaf(s[kvb][r], scale_log2, -m_use));
-                    ps += p;
-                    pf[kvb * 4 + r] = (_Float16)p;
-                }
-            l_run += ps;
+            const sc_h8 pf = dec_softmax_step(s, c * DCH + g * 4, row_end, scale_log2, m_run, l_run, o);
             // ---- O^T += V^T . P^T : V(c) must have landed ----
             asm volatile("s_waitcnt vmcnt(%0)" ::"n"(CNT) : "memory");
-            const unsigned sa = vbase_lds + stage;
             sc_s4 lo[DB], hi[DB];
-#pragma unroll
-            for (int db = 0; db < DB; ++db) {
-                asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(lo[db]) : "v"(sa + v_off[db]));
-                asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(hi[db]) : "v"(sa + v_off[db]), "n"(16 * VROW));
-            }
-            static_assert(DB == 8, "the lgkmcnt fence below names 16 registers");
-            asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(lo[0]), "+v"(hi[0]), "+v"(lo[1]), "+v"(hi[1]), "+v"(lo[2]), "+v"(hi[2]), "+v"(lo[3]), "+v"(hi[3]),
-                                                  "+v"(lo[4]), "+v"(hi[4]), "+v"(lo[5]), "+v"(hi[5]), "+v"(lo[6]), "+v"(hi[6]), "+v"(lo[7]), "+v"(hi[7]) :: "memory");
-            issue_v(c + DEC_PD);                                   // V(c)'s stage is free
-#pragma unroll
-            for (int db = 0; db < DB; ++db) {
-                typedef short sc_s8 __attribute__((ext_vector_type(8)));
-                const sc_s8 v8 = {lo[db][0], lo[db][1], lo[db][2], lo[db][3], hi[db][0], hi[db][1], hi[db][2], hi[db][3]};
-                o[db] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(sc_h8, v8), pf, o[db], 0, 0, 0);
-            }
+            dec_read_vt(vbase_lds + stage, v_off, lo, hi);
+            issue_v(c + DEC_PD);                                   // V(c)'s stage is free: its transposed fragments are in registers
+            dec_pv(lo, hi, pf, o);
         }
     }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");       // no LDS-DMA may still be in flight when the rings are reused / the block ends
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");       // no LDS-DMA may still be in flight when the merge reuses the rings / the block ends
     DEC_STAMP(3);
-    // ---- merge the four waves of the split through LDS (aliases the rings: every wave is done with its own) ----
-    l_run += __shfl_xor(l_run, 16, 64);
-    l_run += __shfl_xor(l_run, 32, 64);
-    __syncthreads();
-    float* mo = reinterpret_cast<float*>(smem);             // [NW][DH][16] O^T, then [NW][16] m, [NW][16] l
-    float* mm = mo + DEC_NW * DH * 16;
-    float* ml = mm + DEC_NW * 16;
-#pragma unroll
-    for (int db = 0; db < DB; ++db)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) mo[(wave * DH + db * 16 + g * 4 + r) * 16 + rl] = o[db][r];
-    if (g == 0) { mm[wave * 16 + rl] = m_run; ml[wave * 16 + rl] = l_run; }
-    __syncthreads();
-    for (int e = tid; e < Sq * DH; e += 64 * DEC_NW) {
-        const int q = e / DH, d = e - q * DH;
-        float M = mm[q];
-#pragma unroll
-        for (int w = 1; w < DEC_NW; ++w) M = fmaxf(M, mm[w * 16 + q]);
-        float acc = 0.f, l = 0.f;
-#pragma unroll
-        for (int w = 0; w < DEC_NW; ++w) {
-            const float mw = mm[w * 16 + q];
-            const float wt = (mw == -INFINITY) ? 0.f : __builtin_amdgcn_exp2f(mw - M);
-            acc += mo[(w * DH + d) * 16 + q] * wt;
-            l += ml[w * 16 + q] * wt;
-        }
-        float* pp = part + ((((size_t)b * Hq + h) * Sq + q) * nsplit + split) * (DH + 2);
-        pp[d] = acc;
-        if (d == 0) { pp[DH] = M; pp[DH + 1] = l; }
-    }
+    dec_merge_waves<DEC_NW, DH>(smem, o, m_run, l_run, tid, wave, rl, g, Sq, part + ((((size_t)b * Hq + h) * Sq) * nsplit + split) * (DH + 2), nsplit);
     DEC_STAMP(4);
 }
 
@@ -369,8 +244,7 @@ void sc_attn_combine_launch(int Dh, const float* part, void* out, int ldo, int B
 
 void sc_attn_decode_launch(const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, int B, int Sq, int Skv, int Hq, int Hkv, float scale_log2,
                            const int32_t* kv_len, float* part, int nsplit, int q_hs, long q_bs, hipStream_t s) {
-    constexpr int LDS_RING = DEC_NW * 2 * DEC_PD * DCH * 128 * 2, LDS_MERGE = DEC_NW * (128 * 16 + 32) * 4;   // NW waves x (K ring + V ring) x DEC_PD stages of 8 KiB
-    constexpr int LDS_DEC = LDS_RING > LDS_MERGE ? LDS_RING : LDS_MERGE;
+    constexpr int LDS_DEC = dec_lds_bytes(DEC_NW * 2 * DEC_PD * DCH * 128 * 2);           // NW waves x (K ring + V ring) x DEC_PD stages of 8 KiB
     sc_set_max_lds<k_attn_decode<128>>(LDS_DEC);
     hipLaunchKernelGGL((k_attn_decode<128>), dim3((unsigned)nsplit, (unsigned)Hq, (unsigned)B), dim3(64 * DEC_NW), LDS_DEC, s, (const _Float16*)q, ldq, (const _Float16*)k, ldk,
                        (const _Float16*)v, ldv, Sq, Skv, Hq, Hkv, scale_log2, kv_len, part, nsplit, q_hs, q_bs, Hq / Hkv);

@@ -1,27 +1,16 @@
 // FP8 (OCP e4m3fn) KV cache for batch-1 decode (include/streamchat_hip_kv8.h): the row quantiser, its inverse, and k_attn_decode of
 // attention_decode.hip over e4m3 bytes.  A cache row is [K of all KV heads | V of all KV heads], 128 bytes per head, and every 128-element
 // segment has one power-of-two fp32 scale 2^e, e in [-14, 7]: code * 2^e is exact in fp16, so the attention kernel converts each operand to
-// exactly the fp16 value k_attn_decode reads from the dequantised cache and feeds the SAME fp16 MFMAs in the same order - its results are
-// bit-identical to that kernel's, the loop just streams half the bytes.  Default machine scheduler, as attention_decode.hip.
-#include "sc_common.h"
+// exactly the fp16 value k_attn_decode reads from the dequantised cache and feeds it to the same functions (attention_decode_common.h: the
+// softmax step, the P.V MFMAs, the merge) in the same order - its results are bit-identical to that kernel's, the loop just streams half the
+// bytes.  Default machine scheduler, as attention_decode.hip.
+#include "attention_decode_common.h"
 #include "../../include/streamchat_hip_kv8.h"
 
 // attention_decode.hip: the split-KV merge, reused unchanged
 void sc_attn_combine_launch(int Dh, const float* part, void* out, int ldo, int B, int Sq, int Hq, int nsplit, int o_hs, long o_bs, hipStream_t s);
 
 namespace {
-
-typedef short sc_s4 __attribute__((ext_vector_type(4)));
-
-// LDS-DMA through a raw buffer resource: every lane's BYTES bytes land lane-linear behind `lds`; an offset at or past `extent` reads zeros
-__device__ __forceinline__ void lds_load16(const void* base, int extent, char* lds, unsigned voff) {
-    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, extent, 0x00020000);
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (__attribute__((address_space(3))) void*)lds, 16, voff, 0, 0, 0);
-}
-__device__ __forceinline__ void lds_load4(const void* base, int extent, char* lds, unsigned voff) {
-    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, extent, 0x00020000);
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (__attribute__((address_space(3))) void*)lds, 4, voff, 0, 0, 0);
-}
 
 // 8 e4m3 bytes -> 8 fp16 values code * s (s = a power of two as a packed fp16 pair: the product is exact, see the header)
 __device__ __forceinline__ sc_h8 cvt8(const sc_u2 w, const sc_h2 s) {
@@ -75,8 +64,8 @@ __global__ __launch_bounds__(256) void k_kv8_dequantize(const uint8_t* __restric
 }
 
 // ------------------------------------------------------------------------------------------------------------------
-// k_attn_decode (attention_decode.hip: 32-row chunks, the even chunk partition over splits and waves, one LDS-DMA ring per wave,
-// hand-counted vmcnt, the end-of-block merge) with e4m3 operands.  Per wave and ring stage:
+// k_attn_decode (attention_decode.hip: one LDS-DMA ring per wave, hand-counted vmcnt) with e4m3 operands; the 32-row chunks, their even
+// partition over splits and waves, the softmax step, P.V and the end-of-block merge are attention_decode_common.h's.  Per wave and ring stage:
 //   K bytes  4 KiB: rows of 128 B row-major, the 16-byte slot XORed with (row >> 1) & 7 on the SOURCE side, so the 8-byte A-fragment reads
 //            (ds_read_b64: bytes ds * 32 + g * 8 .. + 7 of row kvb * 16 + rl, the elements k_attn_decode's lane holds) of a half-wave
 //            cover 256 distinct bytes modulo the bank period;
@@ -84,25 +73,21 @@ __global__ __launch_bounds__(256) void k_kv8_dequantize(const uint8_t* __restric
 //            piece lane % 16: ONE row, one scale per read);
 //   scales   256 B: ONE 4-byte DMA per chunk, lanes 0-31 the K scales of rows 0-31, lanes 32-63 the V scales in the order a lane reads
 //            them (slot w * 8 + i = row i * 4 + w);  it rides in front of the K bytes, so a chunk's scales are there with its K.
-// The converted V chunk (fp16(code * scale), 8 KiB, ONE per wave) is written in exactly k_attn_decode's V ring layout and read with its
-// ds_read_b64_tr_b16 reads; same-wave LDS write -> read needs an lgkmcnt wait and no barrier.  16.25 KiB per wave at DEC8_PD = 1.
+// The converted V chunk (fp16(code * scale), 8 KiB, ONE per wave) is written in exactly k_attn_decode's V ring layout and read with the same
+// ds_read_b64_tr_b16 reads (dec_read_vt); same-wave LDS write -> read needs an lgkmcnt wait and no barrier.  16.25 KiB per wave at DEC8_PD = 1.
 // Rows past the wave's range are outside the extent of ALL THREE buffer resources (bytes and scales): zeros, whatever memory holds there
 // (0 * 0 = 0 in the MFMA; a NaN scale or a NaN byte behind kv_len is never read).
 // vm queue of a wave:  [q x 4]  K(c0) V(c0) ..  then per chunk  K(c + PD)  V(c + PD);  K(c) = 1 scale op + 4 byte ops, V(c) = 4 ops.
 // ------------------------------------------------------------------------------------------------------------------
-constexpr int DCH = 32, DEC8_NW = 4, DEC8_NW_LOG = 2;
-#ifndef SC_DEC8_PD
-#define SC_DEC8_PD 1
-#endif
-constexpr int DEC8_PD = SC_DEC8_PD;
+constexpr int DEC8_PD = 1;                                                       // ring stages (2 measured: profiles/r11_decode_kv8_ab.md)
 constexpr int KB8 = DCH * 128, SCB = 256, VST = DCH * 256;                       // K or V bytes of a chunk, its scales, the fp16 V stage
 constexpr int WAVE_LDS8 = DEC8_PD * (2 * KB8 + SCB) + VST;
 
-__global__ __launch_bounds__(64 * DEC8_NW) void k_attn_kv8(const _Float16* __restrict__ Q, int ldq, const uint8_t* __restrict__ cache, int ldc,
+__global__ __launch_bounds__(64 * DEC_NW) void k_attn_kv8(const _Float16* __restrict__ Q, int ldq, const uint8_t* __restrict__ cache, int ldc,
                                                            const float* __restrict__ scales, int Sq, int Skv, int Hkv, float scale_log2,
                                                            const int* __restrict__ kv_len, float* __restrict__ part, int nsplit, int q_hs) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    constexpr int DH = 128, DS = 4, DB = 8, VROW = 256;
+    constexpr int DH = 128, DS = 4, DB = 8, VROW = DEC_VROW;
     constexpr int CNT_K = 9 * DEC8_PD - 5, CNT_V = 9 * DEC8_PD - 4;                 // vm ops younger than K(c) / than V(c) at their waits
     static_assert(DEC8_PD >= 1 && CNT_V < 64, "vmcnt is a 6-bit counter");
     const int tid = threadIdx.x, lane = tid & 63;
@@ -110,19 +95,10 @@ __global__ __launch_bounds__(64 * DEC8_NW) void k_attn_kv8(const _Float16* __res
     const int rl = lane & 15, g = lane >> 4;
     const int split = blockIdx.x, h = blockIdx.y;
     const int kv_valid = kv_len ? min(max(kv_len[0], 0), Skv) : Skv;
-    const int nch = (kv_valid + DCH - 1) / DCH;
-    const int cq = nch / nsplit, cr = nch - cq * nsplit;                                // the first cr splits take cq + 1 chunks
-    const int s_lo = split * cq + min(split, cr), ns = cq + (split < cr ? 1 : 0);
-    const int c_lo = s_lo + ((ns * wave) >> DEC8_NW_LOG), c_hi = s_lo + ((ns * (wave + 1)) >> DEC8_NW_LOG);
-    const int row_end = min(c_hi * DCH, kv_valid);                                      // rows of this wave: [c_lo * 32, row_end)
-
+    const DecRange wr = dec_range<DEC_NW_LOG>(kv_valid, nsplit, split, wave);
+    const int c_lo = wr.c_lo, c_hi = wr.c_hi, row_end = wr.row_end;                     // (plain ints: the issue lambdas capture them)
     sc_u4 qf[DS];
-    {
-        const int qr = rl < Sq ? rl : Sq - 1;
-        const _Float16* qp = Q + (size_t)qr * (size_t)ldq + h * q_hs + g * 8;
-#pragma unroll
-        for (int ds = 0; ds < DS; ++ds) asm volatile("global_load_dwordx4 %0, %1, off offset:%2" : "=v"(qf[ds]) : "v"(qp), "n"(ds * 64) : "memory");
-    }
+    dec_load_q(Q + h * q_hs, ldq, Sq, rl, g, qf);
     const int nseg = 2 * Hkv;
     const uint8_t* kbase = cache + h * DH;
     const uint8_t* vbase = cache + (Hkv + h) * DH;
@@ -153,10 +129,8 @@ __global__ __launch_bounds__(64 * DEC8_NW) void k_attn_kv8(const _Float16* __res
     unsigned w_off[8];
 #pragma unroll
     for (int i = 0; i < 8; ++i) { const int r = i * 4 + g; w_off[i] = (unsigned)(r * VROW + ((rl ^ ((r & 7) << 1)) << 4)); }
-    const int vrow = 4 * g + (rl >> 2);
     unsigned v_off[DB];
-#pragma unroll
-    for (int db = 0; db < DB; ++db) v_off[db] = (unsigned)(vrow * VROW + ((db ^ (vrow & 7)) << 5) + (rl & 3) * 8);
+    dec_v_offsets(rl, g, v_off);
 
     auto issue_k = [&](int c) {                                  // 1 + 4 LDS-DMA ops
         const int st = c % DEC8_PD;
@@ -210,38 +184,7 @@ __global__ __launch_bounds__(64 * DEC8_NW) void k_attn_kv8(const _Float16* __res
                 for (int ds = 0; ds < DS; ++ds)
                     s[kvb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(cvt8(kb[kvb][ds], ks), __builtin_bit_cast(sc_h8, qf[ds]), s[kvb], 0, 0, 0);
             }
-            // ---- exact online-softmax step (k_attn_decode's, instruction for instruction) ----
-            const int kv0 = c * DCH + g * 4;
-            float tmax = -INFINITY;
-#pragma unroll
-            for (int kvb = 0; kvb < 2; ++kvb)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    s[kvb][r] = (kv0 + kvb * 16 + r < row_end) ? s[kvb][r] : -INFINITY;
-                    tmax = fmaxf(tmax, s[kvb][r]);
-                }
-            const auto a = __builtin_amdgcn_permlane16_swap(__float_as_uint(tmax), __float_as_uint(tmax), false, false);
-            tmax = fmaxf(__uint_as_float(a[0]), __uint_as_float(a[1]));
-            const auto bsw = __builtin_amdgcn_permlane32_swap(__float_as_uint(tmax), __float_as_uint(tmax), false, false);
-            tmax = fmaxf(__uint_as_float(bsw[0]), __uint_as_float(bsw[1])) * scale_log2;
-            const float m_new = fmaxf(m_run, tmax);
-            const float m_use = (m_new == -INFINITY) ? 0.f : m_new;
-            const float alpha = __builtin_amdgcn_exp2f(m_run - m_use);
-            m_run = m_new;
-            l_run *= alpha;
-#pragma unroll
-            for (int db = 0; db < DB; ++db) o[db] *= alpha;
-            sc_h8 pf;
-            float ps = 0.f;
-#pragma unroll
-            for (int kvb = 0; kvb < 2; ++kvb)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const float p = __builtin_amdgcn_exp2f(__builtin_fmaf(s[kvb][r], scale_log2, -m_use));
-                    ps += p;
-                    pf[kvb * 4 + r] = (_Float16)p;
-                }
-            l_run += ps;
+            const sc_h8 pf = dec_softmax_step(s, c * DCH + g * 4, row_end, scale_log2, m_run, l_run, o);
             // ---- V(c) must have landed: bytes -> fp16(code * scale) -> the fp16 stage ----
             asm volatile("s_waitcnt vmcnt(%0)" ::"n"(CNT_V) : "memory");
             sc_u2 vb[8];
@@ -259,52 +202,12 @@ __global__ __launch_bounds__(64 * DEC8_NW) void k_attn_kv8(const _Float16* __res
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             // ---- O^T += V^T . P^T ----
             sc_s4 lo[DB], hi[DB];
-#pragma unroll
-            for (int db = 0; db < DB; ++db) {
-                asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(lo[db]) : "v"(st_lds + v_off[db]) : "memory");
-                asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(hi[db]) : "v"(st_lds + v_off[db]), "n"(16 * VROW) : "memory");
-            }
-            asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(lo[0]), "+v"(hi[0]), "+v"(lo[1]), "+v"(hi[1]), "+v"(lo[2]), "+v"(hi[2]), "+v"(lo[3]), "+v"(hi[3]),
-                                                  "+v"(lo[4]), "+v"(hi[4]), "+v"(lo[5]), "+v"(hi[5]), "+v"(lo[6]), "+v"(hi[6]), "+v"(lo[7]), "+v"(hi[7]) :: "memory");
-#pragma unroll
-            for (int db = 0; db < DB; ++db) {
-                typedef short sc_s8 __attribute__((ext_vector_type(8)));
-                const sc_s8 v8 = {lo[db][0], lo[db][1], lo[db][2], lo[db][3], hi[db][0], hi[db][1], hi[db][2], hi[db][3]};
-                o[db] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(sc_h8, v8), pf, o[db], 0, 0, 0);
-            }
+            dec_read_vt(st_lds, v_off, lo, hi);
+            dec_pv(lo, hi, pf, o);
         }
     }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");       // no LDS-DMA may still be in flight when the rings are reused / the block ends
-    // ---- merge the four waves of the split through LDS (aliases the rings: every wave is done with its own) ----
-    l_run += __shfl_xor(l_run, 16, 64);
-    l_run += __shfl_xor(l_run, 32, 64);
-    __syncthreads();
-    float* mo = reinterpret_cast<float*>(smem);             // [NW][DH][16] O^T, then [NW][16] m, [NW][16] l
-    float* mm = mo + DEC8_NW * DH * 16;
-    float* ml = mm + DEC8_NW * 16;
-#pragma unroll
-    for (int db = 0; db < DB; ++db)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) mo[(wave * DH + db * 16 + g * 4 + r) * 16 + rl] = o[db][r];
-    if (g == 0) { mm[wave * 16 + rl] = m_run; ml[wave * 16 + rl] = l_run; }
-    __syncthreads();
-    for (int e = tid; e < Sq * DH; e += 64 * DEC8_NW) {
-        const int q = e / DH, d = e - q * DH;
-        float M = mm[q];
-#pragma unroll
-        for (int w = 1; w < DEC8_NW; ++w) M = fmaxf(M, mm[w * 16 + q]);
-        float acc = 0.f, l = 0.f;
-#pragma unroll
-        for (int w = 0; w < DEC8_NW; ++w) {
-            const float mw = mm[w * 16 + q];
-            const float wt = (mw == -INFINITY) ? 0.f : __builtin_amdgcn_exp2f(mw - M);
-            acc += mo[(w * DH + d) * 16 + q] * wt;
-            l += ml[w * 16 + q] * wt;
-        }
-        float* pp = part + (((size_t)h * Sq + q) * nsplit + split) * (DH + 2);
-        pp[d] = acc;
-        if (d == 0) { pp[DH] = M; pp[DH + 1] = l; }
-    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");       // no LDS-DMA may still be in flight when the merge reuses the rings / the block ends
+    dec_merge_waves<DEC_NW, DH>(smem, o, m_run, l_run, tid, wave, rl, g, Sq, part + (((size_t)h * Sq) * nsplit + split) * (DH + 2), nsplit);
 }
 
 }  // namespace
@@ -366,10 +269,9 @@ extern "C" int sc_attention_kv8(const void* q, int ldq, const uint8_t* cache, in
     SC_REQUIRE(qhs % 8 == 0 && ohs % 4 == 0, "sc_attention_kv8: head strides must be multiples of 8 (q) / 4 (out)");
     hipStream_t s = (hipStream_t)stream;
     const float sl2 = (flags & SC_ATTN_Q_PRESCALED) ? 1.0f : scale * 1.4426950408889634f;
-    constexpr int LDS_RING = DEC8_NW * WAVE_LDS8, LDS_MERGE = DEC8_NW * (128 * 16 + 32) * 4;
-    constexpr int LDS = LDS_RING > LDS_MERGE ? LDS_RING : LDS_MERGE;
+    constexpr int LDS = dec_lds_bytes(DEC_NW * WAVE_LDS8);
     sc_set_max_lds<k_attn_kv8>(LDS);
-    hipLaunchKernelGGL(k_attn_kv8, dim3((unsigned)nsplit, (unsigned)kv_heads), dim3(64 * DEC8_NW), LDS, s, (const _Float16*)q, ldq, cache, cache_ld, scales, Sq, Skv,
+    hipLaunchKernelGGL(k_attn_kv8, dim3((unsigned)nsplit, (unsigned)kv_heads), dim3(64 * DEC_NW), LDS, s, (const _Float16*)q, ldq, cache, cache_ld, scales, Sq, Skv,
                        kv_heads, sl2, kv_len, (float*)ws, nsplit, qhs);
     sc_attn_combine_launch(128, (const float*)ws, out, ldo, 1, Sq, kv_heads, nsplit, ohs, (long)Sq * ldo, s);
     SC_CHECK_LAUNCH("sc_attention_kv8");

@@ -70,6 +70,23 @@ def attention_case(S, G, kv_heads, seed):
     return codes, scale, q
 
 
+# (S, G, nsplit) of tests/golden/decode_attention_bits.npz (tools/make_golden_decode_bits.py records it, tests/test_gpu_kv8.py reads it), the
+# smallest shapes at which each piece that the two decode attention kernels share can go wrong: one partial chunk with empty waves and an empty
+# split | a chunk boundary with a one-row masked tail and Sq < 16 | more splits than chunks | uneven chunk shares across waves and splits
+# (twice) | the production split rule (None: llm.decode_nsplit(128, S)).  Hkv = 2, q pre-scaled, inputs from decode_bits_inputs.
+DECODE_BITS_CASES = [(1, 1, 2), (33, 7, 2), (33, 16, 5), (769, 1, 3), (769, 16, 5), (2273, 7, None)]
+
+
+def decode_bits_inputs(S, G):
+    """(codes, scale, q, crc): the generated inputs of one DECODE_BITS_CASES case and the CRC32 of their bytes"""
+    import zlib
+    codes, scale, q = attention_case(S, G, 2, seed=100 + S + G)
+    crc = 0
+    for t in (codes, scale, q):
+        crc = zlib.crc32(t.contiguous().numpy().tobytes(), crc)
+    return codes, scale, q, crc
+
+
 def attention_fp64(q, codes, scale, kv_heads, kv_len=None, values=_w8.e4m3_values, scale_k=None, scale_v=None):
     """fp64 decode attention of pre-scaled q (logits in log2 units, as the kernels take them) over the dequantised cache -> [G, kv_heads * 128].
     `values`, `scale_k`, `scale_v` ([S, kv_heads] each): what a WRONG kernel would use; kv_len: rows past it are masked."""

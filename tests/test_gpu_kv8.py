@@ -124,6 +124,25 @@ def test_attention_kv8_is_bit_identical_to_the_fp16_kernel_on_the_dequantised_ca
         assert bool(torch.isfinite(a).all()) and ((a.cpu().double() - ref).abs().max() / ref.abs().max()).item() < 2e-2      # and both are an attention at all
 
 
+@pytest.mark.parametrize("S,G,nsplit", _kv8.DECODE_BITS_CASES)
+def test_decode_attention_keeps_its_recorded_bits(S, G, nsplit):
+    """both kernels take the chunk partition, softmax step, P.V accumulation and wave merge from attention_decode_common.h, so the comparison
+    above cannot see a mistake in that text; tests/golden/decode_attention_bits.npz holds what k_attn_decode + k_attn_combine gave before the
+    two kernels shared it (tools/make_golden_decode_bits.py)"""
+    import os
+    import numpy as np
+    nsplit = nsplit or LM.decode_nsplit(DH, S)
+    d = np.load(os.path.join(os.path.dirname(__file__), "golden", "decode_attention_bits.npz"))
+    codes, scale, q, crc = _kv8.decode_bits_inputs(S, G)
+    assert crc == int(d[f"crc_{S}_{G}_{nsplit}"]), "the input generator drifted (not a kernel failure): re-record tests/golden/decode_attention_bits.npz"
+    want = torch.from_numpy(d[f"bits_{S}_{G}_{nsplit}"].view(np.int16))
+    a, b = _attend_both(codes, scale, q, 2, nsplit, pad=128)
+    assert ops.attention_variant(DH, G, nsplit) == 3
+    for name, got in (("ops.attention on the dequantised cache", b), ("ops.attention_kv8", a)):
+        n = int((_bits(got) != want).sum())
+        assert n == 0, f"{name}, S={S} G={G} nsplit={nsplit}: {n} of {want.numel()} elements differ from the recorded bits"
+
+
 def test_poisoned_tail_contributes_nothing():
     """kv_len (device) below the allocated rows; the bytes behind it are 0x7F (NaN), their scales NaN: the result equals the unpoisoned one"""
     Hkv, G, S, extra = 2, 7, 777, 60
