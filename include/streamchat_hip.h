@@ -197,7 +197,7 @@ enum { SC_EPI_NONE = 0, SC_EPI_QUICK_GELU = 1, SC_EPI_GELU_ERF = 2, SC_EPI_SWIGL
  * lda % 8 == 0.  M is arbitrary.  bias and residual may be NULL.
  * out_flags: SC_GEMM_OUT_F32 (= 1, what `out_f32 = 1` always meant) | SC_GEMM_DISPATCH_ROWS(m), m >= M: choose the kernel as for a GEMM of m rows
  * and compute M rows.  Which kernel runs depends on the row count (M <= 32: weight-streaming kernels, M >= 1024: 256 x 256 tiles, between:
- * 128 x 128 tiles) and the kernels round differently in the last bit; within one kernel an output element depends on its own row of A
+ * 128 x 128 tiles, or 64 x 64 tiles out of an LDS ring that sum in the same order and give the same bits) and the kernels round differently in the last bit; within one kernel an output element depends on its own row of A
  * alone.  So rows [r0, r0 + M) of an m-row GEMM, launched on their own with this hint, are bit-identical to the same rows of the m-row launch.
  * Optional A row-group map (a_grp > 0): logical row m reads storage row
  * (m / a_grp) * a_grp_stride + a_grp_off + m % a_grp  — e.g. (576, 577, 1) drops the CLS token of every

@@ -88,6 +88,19 @@ KV8_SIGNATURES = {
                                  c_void_p, c_size_t, c_int, c_int, c_void_p]),
 }
 
+# include/streamchat_hip_text.h - a whole text-encoder forward from one call: a third additive extension header with a table of its own (base
+# ABI 9 and the three tables above are untouched); bound in load() like every other symbol
+class TextEncoderLayer(ctypes.Structure):
+    """sc_text_encoder_layer: device pointers of one post-LN encoder layer"""
+    _fields_ = [(n, c_void_p) for n in ("wqkv", "bqkv", "wo", "bo", "ln1_g", "ln1_b", "w1", "b1", "w2", "b2", "ln2_g", "ln2_b")]
+
+
+TEXT_SIGNATURES = {
+    "sc_text_encoder_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "sc_text_encoder_f16": (c_int, [POINTER(TextEncoderLayer), c_int, c_int, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
+                                    c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
+}
+
 _lib = None
 
 
@@ -108,7 +121,7 @@ def load():
     except ImportError:
         pass
     lib = ctypes.CDLL(LIB_PATH)
-    for name, (res, args) in list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()) + list(KV8_SIGNATURES.items()):
+    for name, (res, args) in list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()) + list(KV8_SIGNATURES.items()) + list(TEXT_SIGNATURES.items()):
         try:
             fn = getattr(lib, name)
         except AttributeError as e:

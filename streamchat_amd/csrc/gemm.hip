@@ -7,7 +7,8 @@
 // MFMA operands are read along K with 16-byte ds_read_b128.
 //
 // Three generations live here: k_gemm_fat (v3, below: the default for the large GEMMs), k_gemm256 (v2: 8 waves, K = 32 ring; now the
-// fallback for K % 128 != 0, fp32 output and the row-mapped A operand), k_gemm128 (v1: small M / N % 256 != 0) and k_gemm_skinny (M <= 32).
+// fallback for K % 128 != 0, fp32 output and the row-mapped A operand), k_gemm128 (v1: small M / N % 256 != 0), k_gemm_mid (32 < M < 1024 with
+// K >= 512: k_gemm128's sums out of a four-stage LDS ring on 64 x 64 tiles) and k_gemm_skinny (M <= 32).
 //
 // Structure (v1): 128x128x64 block tile, 256 threads = 4 waves (2x2), each wave 64x64 = 4x4 fragments of
 // v_mfma_f32_16x16x32_f16 (fp32 accumulate).  Tiles are staged HBM->LDS with 16-byte
@@ -1274,6 +1275,149 @@ __global__ __launch_bounds__(256) void k_gemm_skinny_lx(const _Float16* __restri
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 }
 
+// ------------------------------------------------------------------------------------------------------------------
+// k_gemm_mid - between k_gemm_skinny (M <= 32) and the 256 x 256 kernels (M >= 1024): the text encoders' caption / document batches, a single
+// ViT frame, short text-only prefills.  k_gemm128 puts 16 - 32 workgroups on 256 CUs at these shapes and pays a full HBM latency per 64-deep K
+// step (its two LDS stages are separated by a __syncthreads() that drains the DMA queue).  Here:
+//   * 64 x 64 tile, 4 waves (2 x 2, each 32 x 32 = 2 x 2 MFMA fragments): four times the workgroups of k_gemm128 (64 x 128 is a compile-time
+//     variant, SC_GEMM_MID_BN: measured, not faster - profiles/r12_text_encoder_native_ab.md);
+//   * K in 64-deep steps through an LDS ring of MID_NS stages (16 KiB each), filled by 16-byte buffer_load ... lds; step k + MID_NS - 1 is issued
+//     right after the ONE raw s_barrier of step k, which (a) publishes step k - every wave has waited, with a counted vmcnt, for its own share
+//     of it - and (b) proves nobody still reads the slot of step k - 1 that the new DMA overwrites.  MID_NS - 2 steps stay in flight across it;
+//   * every iteration is identical: steps past K are issued with a zero buffer extent (no memory traffic, zeros into a free slot), so the
+//     counted wait is the same immediate from the first step to the last;
+//   * rows >= M read as zeros through the buffer extent of the tile's A rows and are never stored.
+// Summation order - the contract: k_gemm128's.  The LDS image of an operand tile is k_gemm128's (same granule -> (row, k-slot) map, same
+// swizzle), the fragments are read with the same addresses, so lane group g, element e holds k = 32 * step + 8 g + e; one
+// v_mfma_f32_16x16x32_f16 chain per output element over K ascending from a zero accumulator, W fragment first; the epilogue is the same
+// expression (bias add, activation, residual add in fp32, one rounding).  The output is bit-identical to k_gemm128's.
+// ------------------------------------------------------------------------------------------------------------------
+#ifndef SC_GEMM_MID_NS
+#define SC_GEMM_MID_NS 4      // ring stages
+#endif
+#ifndef SC_GEMM_MID_BN
+#define SC_GEMM_MID_BN 64     // tile columns: 64 or 128 (measured: profiles/r12_text_encoder_native_ab.md)
+#endif
+constexpr int MID_BM = 64, MID_BN = SC_GEMM_MID_BN, MID_NS = SC_GEMM_MID_NS;
+constexpr int MID_TILE = MID_BM * BK * 2;         // A: 8 KiB per stage
+constexpr int MID_WTILE = MID_BN * BK * 2;        // W: 8 or 16 KiB per stage
+constexpr int MID_STAGE = MID_TILE + MID_WTILE;
+constexpr int MID_NW = MID_BN / 32;               // W granules per thread and stage (A: 2) = MFMA fragment columns per wave
+static_assert(MID_BN == 64 || MID_BN == 128, "k_gemm_mid: 64 x 64 or 64 x 128 tiles");
+static_assert(MID_NS >= 4 && MID_NS * MID_STAGE <= 160 * 1024 && (2 + MID_NW) * (MID_NS - 2) < 64, "k_gemm_mid: ring of at least four stages inside the LDS, counted wait within vmcnt's range");
+
+template <int EPI>
+__global__ __launch_bounds__(256, 2) void k_gemm_mid(const _Float16* __restrict__ A, int lda, const _Float16* __restrict__ W,
+                                                     const _Float16* __restrict__ bias, const _Float16* __restrict__ R, int ldr,
+                                                     _Float16* __restrict__ C, int ldc, int M, int N, int K, int tilesM) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    // XCD-contiguous block remap (as k_gemm128), the row tile fastest: the workgroups that share a W tile run on one XCD, next to each other
+    const int nwg = gridDim.x, bid = blockIdx.x;
+    const int xcd = bid & 7, q8 = nwg >> 3, r8 = nwg & 7;
+    const int swz = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
+    const int tn = swz / tilesM, tm = swz - tn * tilesM;
+
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int wm = wave >> 1, wn = wave & 1;
+
+    // staging (k_gemm128's granule map): granule q = i * 256 + tid (i < 2) of an operand tile sits at LDS byte q * 16 and holds logical
+    // (row 2 * (q >> 4) + ((q & 15) >> 3), k-slot (q & 7) ^ ((q >> 4) & 7))
+    const int srow = 2 * (tid >> 4) + ((tid >> 3) & 1);
+    const int sslot = (tid & 7) ^ ((tid >> 4) & 7);
+    const int a_rows = (M - tm * MID_BM) < MID_BM ? (M - tm * MID_BM) : MID_BM;
+    const _Float16* At = A + (size_t)tm * MID_BM * (size_t)lda;
+    const _Float16* Wt = W + (size_t)tn * MID_BN * (size_t)K;
+    const unsigned a_ext = (unsigned)a_rows * (unsigned)lda * 2u, w_ext = (unsigned)MID_BN * (unsigned)K * 2u;
+    unsigned a_vo[2], w_vo[MID_NW];
+#pragma unroll
+    for (int i = 0; i < 2; ++i) a_vo[i] = ((unsigned)(i * 32 + srow) * (unsigned)lda + (unsigned)(sslot * 8)) * 2u;
+#pragma unroll
+    for (int i = 0; i < MID_NW; ++i) w_vo[i] = ((unsigned)(i * 32 + srow) * (unsigned)K + (unsigned)(sslot * 8)) * 2u;
+    const int nk = K / BK;
+    auto stage = [&](int ks) {                      // 2 + MID_NW DMA instructions per thread and step; ks >= nk: extent 0, nothing is fetched
+        char* base = smem + (ks % MID_NS) * MID_STAGE;
+        const bool live = ks < nk;
+        const unsigned ko = (unsigned)ks * (unsigned)(BK * 2);
+#pragma unroll
+        for (int i = 0; i < 2; ++i) lds_load16(At, live ? a_ext : 0u, base + (i * 256 + wave * 64) * 16, a_vo[i], ko);
+#pragma unroll
+        for (int i = 0; i < MID_NW; ++i) lds_load16(Wt, live ? w_ext : 0u, base + MID_TILE + (i * 256 + wave * 64) * 16, w_vo[i], ko);
+    };
+
+    // fragment read addresses (bytes inside an operand tile), as k_gemm128
+    const int rl = lane & 15, g = lane >> 4;
+    const int sw = (rl >> 1) & 7;
+    const int slot0 = ((sw >> 2) << 2) | (g ^ (sw & 3));
+    const int frag_off = (rl >> 1) * 256 + ((rl & 1) << 7) + slot0 * 16;
+    const int a_base = wm * 32 * 128 + frag_off;
+    const int b_base = MID_TILE + wn * (MID_BN / 2) * 128 + frag_off;
+
+    sc_f4 acc[2][MID_NW];
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < MID_NW; ++j) acc[i][j] = sc_f4{0.f, 0.f, 0.f, 0.f};
+
+#pragma unroll
+    for (int p = 0; p < MID_NS - 1; ++p) stage(p);
+    for (int ks = 0; ks < nk; ++ks) {
+        // at most the MID_NS - 2 youngest steps of this thread's DMA stay in flight: step ks has landed
+        asm volatile("s_waitcnt vmcnt(%0)" ::"n"((2 + MID_NW) * (MID_NS - 2)) : "memory");
+        __builtin_amdgcn_s_barrier();
+        stage(ks + MID_NS - 1);                      // into the slot of step ks - 1
+        const char* sb = smem + (ks % MID_NS) * MID_STAGE;
+#pragma unroll
+        for (int kk = 0; kk < 2; ++kk) {
+            sc_h8 a[2], b[MID_NW];
+#pragma unroll
+            for (int i = 0; i < 2; ++i) a[i] = *reinterpret_cast<const sc_h8*>(sb + ((a_base ^ (kk * 64)) + i * 2048));
+#pragma unroll
+            for (int j = 0; j < MID_NW; ++j) b[j] = *reinterpret_cast<const sc_h8*>(sb + ((b_base ^ (kk * 64)) + j * 2048));
+#pragma unroll
+            for (int i = 0; i < 2; ++i)
+#pragma unroll
+                for (int j = 0; j < MID_NW; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(b[j], a[i], acc[i][j], 0, 0, 0);
+        }
+    }
+
+    // epilogue (k_gemm128's): lane holds C[m][n .. n+3] for m = m0 + mi*16 + rl, n = n0 + nj*16 + g*4
+    const int m0 = tm * MID_BM + wm * 32, n0 = tn * MID_BN + wn * (MID_BN / 2);
+#pragma unroll
+    for (int nj = 0; nj < MID_NW; ++nj) {
+        const int n = n0 + nj * 16 + g * 4;
+        float bv[4] = {0.f, 0.f, 0.f, 0.f};
+        if (bias) {
+            sc_h4 b4 = *reinterpret_cast<const sc_h4*>(bias + n);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) bv[e] = (float)b4[e];
+        }
+#pragma unroll
+        for (int mi = 0; mi < 2; ++mi) {
+            const int m = m0 + mi * 16 + rl;
+            if (m < M) {
+                float v[4];
+#pragma unroll
+                for (int e = 0; e < 4; ++e) v[e] = epi_apply(acc[mi][nj][e] + bv[e], EPI);
+                if (R) {
+                    sc_h4 r4 = *reinterpret_cast<const sc_h4*>(R + (size_t)m * (size_t)ldr + n);
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) v[e] += (float)r4[e];
+                }
+                sc_h4 o = {(_Float16)v[0], (_Float16)v[1], (_Float16)v[2], (_Float16)v[3]};
+                *reinterpret_cast<sc_h4*>(C + (size_t)m * (size_t)ldc + n) = o;
+            }
+        }
+    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the zero-extent DMA of the last steps retires before the LDS is released
+}
+
+// SC_GEMM_MID=0 pins the dispatch without k_gemm_mid (the reference of tests/test_gpu_gemm_mid.py and an A/B switch); read once per process
+bool gemm_mid_enabled() {
+    static const bool on = [] { const char* e = getenv("SC_GEMM_MID"); return !(e && e[0] == '0'); }();
+    return on;
+}
+
 // raster group of the 256x256-tile kernels: GM tile-rows, 4 for wide N (A/B in profiles/)
 constexpr int raster_group(int tilesN) { return tilesN > 16 ? 4 : SC_GEMM_GM; }
 
@@ -1381,6 +1525,19 @@ int launch_gemm(const void* A, int lda, const void* W, const void* bias, const v
         SC_CHECK_LAUNCH("sc_gemm_f16");
         return SC_OK;
     }
+    // between the two: k_gemm_mid for fp16 output without the A row map, plain / activation epilogues, a ring's worth of K and operands its
+    // 16-byte DMA and 32-bit buffer offsets can address; bit-identical to k_gemm128 below, which keeps everything else
+    if constexpr (EPI == SC_EPI_NONE || EPI == SC_EPI_QUICK_GELU || EPI == SC_EPI_GELU_ERF)
+        if (gemm_mid_enabled() && Md > 32 && Md < 1024 && !out_f32 && a_grp == 0 && K >= 512 && lda % 8 == 0 && (size_t)lda * (2 * MID_BM) < (1ull << 31) &&
+            (size_t)K * (2 * MID_BN) < (1ull << 31) && ((reinterpret_cast<uintptr_t>(A) | reinterpret_cast<uintptr_t>(W)) & 15) == 0) {
+            const int tM = (M + MID_BM - 1) / MID_BM;
+            constexpr int LDSM = MID_NS * MID_STAGE;
+            sc_set_max_lds<k_gemm_mid<EPI>>(LDSM);
+            hipLaunchKernelGGL((k_gemm_mid<EPI>), dim3((unsigned)(tM * (N / MID_BN))), dim3(256), LDSM, s, (const _Float16*)A, lda, (const _Float16*)W,
+                               (const _Float16*)bias, (const _Float16*)R, ldr, (_Float16*)C, ldc, M, N, K, tM);
+            SC_CHECK_LAUNCH("sc_gemm_f16");
+            return SC_OK;
+        }
     const int tilesM = (M + BM - 1) / BM, tilesN = N / BN;
     const dim3 grid((unsigned)(tilesM * tilesN)), block(256);
     const size_t lds = 2 * STAGE_BYTES;

@@ -683,6 +683,41 @@ def bert_embed_ln(ids, word, pos, type0, gamma, beta, eps: float, out=None):
     return out
 
 
+def text_encoder_layers(layers):
+    """ctypes table for text_encoder() from a list of per-layer dicts of fp16 CUDA tensors (keys: the fields of sc_text_encoder_layer).  Built
+    once per model; the caller keeps the tensors alive."""
+    arr = (_lib.TextEncoderLayer * len(layers))()
+    for a, L in zip(arr, layers):
+        for name, _ in _lib.TextEncoderLayer._fields_:
+            t = L[name]
+            _require_cuda(t)
+            if t.dtype != torch.float16 or not t.is_contiguous():
+                raise StreamChatHipError(f"text_encoder_layers: {name} must be a contiguous fp16 tensor")
+            setattr(a, name, t.data_ptr())
+    return arr
+
+
+def text_encoder(table, hidden: int, heads: int, intermediate: int, eps: float, word, pos, type0, gamma, beta, ids, kv_len=None):
+    """ids int32 [B, L] -> last hidden state fp16 [B * L, hidden] of a post-LN encoder stack (HF BertModel arithmetic) in ONE call of the
+    library (sc_text_encoder_f16): the launches of bert_embed_ln + per layer gemm, attention, gemm, layernorm, gemm, gemm, layernorm, bit for bit.
+    `table`: text_encoder_layers(...); kv_len int32 [B] (device) or None."""
+    _require_cuda(ids, word, pos, type0, gamma, beta, kv_len)
+    lib = _lib.load()
+    B, L = ids.shape
+    M, H, I = B * L, hidden, intermediate
+    dev = word.device
+    ids = ids.to(torch.int32).contiguous()
+    kv_len = None if kv_len is None else kv_len.to(torch.int32).contiguous()
+    out = torch.empty((M, H), dtype=torch.float16, device=dev)
+    ws = _workspace(lib.sc_text_encoder_workspace_bytes(M, H, I), dev)
+    n = len(table)
+    flops = n * (2.0 * M * (4.0 * H * H + 2.0 * H * I) + 4.0 * B * L * L * H)
+    with torch.cuda.device(dev), _timed("k_text_encoder", flops):
+        check(lib.sc_text_encoder_f16(table, n, H, heads, I, c_float(eps), ptr(word), ptr(pos), ptr(type0), ptr(gamma), ptr(beta), word.shape[0],
+                                      ptr(ids), ptr(kv_len), B, L, ptr(out), ptr(ws), c_size_t(ws.numel()), stream_ptr(dev)), "sc_text_encoder_f16")
+    return out
+
+
 def pool(hidden, lengths=None, mode: str = "cls", normalize: bool = False):
     """hidden fp16 [B, L, H] -> fp32 [B, H]: CLS row or masked mean (+ optional L2 normalisation)."""
     _require_cuda(hidden)

@@ -69,15 +69,22 @@ class BertEncoder:
                 w1=q(lp + "intermediate.dense.weight"), b1=q(lp + "intermediate.dense.bias"),
                 w2=q(lp + "output.dense.weight"), b2=q(lp + "output.dense.bias"),
                 ln2=(q(lp + "output.LayerNorm.weight"), q(lp + "output.LayerNorm.bias"))))
+        # the same tensors as the pointer table of the one-call forward (built once; self.L keeps them alive)
+        self.table = ops.text_encoder_layers([dict(L, ln1_g=L["ln1"][0], ln1_b=L["ln1"][1], ln2_g=L["ln2"][0], ln2_b=L["ln2"][1]) for L in self.L])
 
-    def forward(self, input_ids, lengths=None):
-        """input_ids [B, L] (right-padded), lengths [B] valid tokens -> last_hidden_state [B, L, H] fp16."""
+    def forward(self, input_ids, lengths=None, layerwise=False):
+        """input_ids [B, L] (right-padded), lengths [B] valid tokens -> last_hidden_state [B, L, H] fp16.
+        One call of the library for the whole stack (ops.text_encoder); layerwise=True issues the same launches one `ops` call at a time -
+        the same bits, the reference body for the tests."""
         c = self.cfg
         B, Ls = input_ids.shape
         H = c.hidden
         ids = input_ids.to(self.device)
-        x = ops.bert_embed_ln(ids, self.word, self.pos, self.type0, self.eg, self.eb, c.eps)
         kv = None if lengths is None else torch.as_tensor(lengths, dtype=torch.int32, device=self.device)
+        if not layerwise:
+            return ops.text_encoder(self.table, H, c.heads, c.intermediate, c.eps, self.word, self.pos, self.type0, self.eg, self.eb, ids,
+                                    kv).view(B, Ls, H)
+        x = ops.bert_embed_ln(ids, self.word, self.pos, self.type0, self.eg, self.eb, c.eps)
         for L in self.L:
             qkv = ops.gemm(x, L["wqkv"], L["bqkv"]).view(B, Ls, 3 * H)
             att = ops.attention(qkv[..., :H], qkv[..., H:2 * H], qkv[..., 2 * H:], c.heads, c.heads, self.dh, self.dh ** -0.5,
