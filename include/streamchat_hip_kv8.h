@@ -15,6 +15,10 @@
  * Extension changelog (additive; base ABI 9 - sc_abi_version() and SC_ABI_VERSION of streamchat_hip.h are unchanged, a binding that does
  * not use these symbols is unaffected; one that does looks the three symbols up and fails if the library lacks them):
  *   kv8-1  + sc_kv8_quantize_rows, sc_kv8_dequantize_rows, sc_attention_kv8
+ *   kv8-2  + sc_attention_kv8_batched, sc_kv8_rope_qkv_rows: the cache of the BATCHED decode (llm.BatchDecoder(kv_cache="fp8")).  Purely additive:
+ *            the three symbols above keep their signatures and their bits (sc_attention_kv8 is now the B = 1 launch of the batched kernel).  The
+ *            two are declared in streamchat_hip_kv8_batched.h, which includes this header: the set of symbols THIS file declares is what a kv8-1
+ *            binding checks itself against (tests/test_kv8_cpu.py) and stays as it is.
  *
  * Conventions: those of streamchat_hip.h.  Head dim 128 only: anything else is SC_ERR_UNSUPPORTED with a message before any device work.
  */

@@ -92,8 +92,13 @@ def parse_args(argv=None):
     p.add_argument("--kv_cache", type=str, choices=["fp16", "fp8"], default="fp16",
                    help="format of the batch-1 KV cache of every model of the process: fp8 = OCP e4m3 bytes with one power-of-two scale per (row, KV "
                         "head, K or V), half the K/V bytes per decode token and 0.57 of the cache's memory (an accuracy trade, off by default: ~2.65 %% "
-                        "relative rms error per segment; head dim 128 only; batched captions and beam search keep fp16 caches).  A decoding setting like "
+                        "relative rms error per segment; head dim 128 only; batched captions and beam search keep fp16 caches unless --batch_kv_cache fp8).  A decoding setting like "
                         "--decode_weights: not part of the memory fingerprint")
+    p.add_argument("--batch_kv_cache", type=str, choices=["fp16", "fp8"], default="fp16",
+                   help="format of the caches of the BATCHED decode of every model of the process (the chunk captions of --batch_captions 1, beam search): "
+                        "fp8 = the e4m3 format of --kv_cache, about half the K/V bytes per step and 0.516 of the caches' memory.  An accuracy trade, off "
+                        "by default (~2.65 %% relative rms error per segment; head dim 128 only): captions and beams may differ from an fp16 run.  "
+                        "Independent of --kv_cache; a decoding setting like it: not part of the memory fingerprint")
     args = p.parse_args(argv)
     if args.num_beams != 1 and (args.temperature or 0) > 0:
         # the reference forwards num_beams and do_sample = (temperature > 0) to HF generate (:252-256): with both that is HF's beam SAMPLING, which
@@ -139,6 +144,10 @@ def build_models(args):
         for m in built:
             if isinstance(getattr(m, "lm", None), LM.Qwen2Model):
                 m.lm.set_kv_cache("fp8")
+    if getattr(args, "batch_kv_cache", "fp16") == "fp8":
+        for m in built:
+            if isinstance(getattr(m, "lm", None), LM.Qwen2Model):
+                m.lm.set_batch_kv_cache("fp8")
     return built
 
 

@@ -88,6 +88,15 @@ KV8_SIGNATURES = {
                                  c_void_p, c_size_t, c_int, c_int, c_void_p]),
 }
 
+# include/streamchat_hip_kv8_batched.h - changelog entry kv8-2: the FP8 KV cache of the BATCHED decode step.  Additive again, with a table of its
+# own (KV8_SIGNATURES is the symbol set of streamchat_hip_kv8.h itself and stays as it is); bound in load() like every other symbol
+KV8_BATCHED_SIGNATURES = {
+    "sc_attention_kv8_batched": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int64, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_int,
+                                         c_void_p, c_int, c_void_p, c_size_t, c_int, c_int, c_int64, c_int64, c_void_p]),
+    "sc_kv8_rope_qkv_rows": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int64, c_int,
+                                     c_void_p, c_int, c_void_p]),
+}
+
 # include/streamchat_hip_text.h - a whole text-encoder forward from one call: a third additive extension header with a table of its own (base
 # ABI 9 and the three tables above are untouched); bound in load() like every other symbol
 class TextEncoderLayer(ctypes.Structure):
@@ -121,7 +130,7 @@ def load():
     except ImportError:
         pass
     lib = ctypes.CDLL(LIB_PATH)
-    for name, (res, args) in list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()) + list(KV8_SIGNATURES.items()) + list(TEXT_SIGNATURES.items()):
+    for name, (res, args) in list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()) + list(KV8_SIGNATURES.items()) + list(KV8_BATCHED_SIGNATURES.items()) + list(TEXT_SIGNATURES.items()):
         try:
             fn = getattr(lib, name)
         except AttributeError as e:

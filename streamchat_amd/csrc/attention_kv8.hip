@@ -1,11 +1,11 @@
-// FP8 (OCP e4m3fn) KV cache for batch-1 decode (include/streamchat_hip_kv8.h): the row quantiser, its inverse, and k_attn_decode of
-// attention_decode.hip over e4m3 bytes.  A cache row is [K of all KV heads | V of all KV heads], 128 bytes per head, and every 128-element
+// FP8 (OCP e4m3fn) KV cache for the batch-1 and the batched decode (include/streamchat_hip_kv8.h, streamchat_hip_kv8_batched.h): the row
+// quantiser, its inverse, the batched step's rotary + quantised append, and k_attn_decode of attention_decode.hip over e4m3 bytes.  A cache row is [K of all KV heads | V of all KV heads], 128 bytes per head, and every 128-element
 // segment has one power-of-two fp32 scale 2^e, e in [-14, 7]: code * 2^e is exact in fp16, so the attention kernel converts each operand to
 // exactly the fp16 value k_attn_decode reads from the dequantised cache and feeds it to the same functions (attention_decode_common.h: the
 // softmax step, the P.V MFMAs, the merge) in the same order - its results are bit-identical to that kernel's, the loop just streams half the
 // bytes.  Default machine scheduler, as attention_decode.hip.
 #include "attention_decode_common.h"
-#include "../../include/streamchat_hip_kv8.h"
+#include "../../include/streamchat_hip_kv8_batched.h"
 
 // attention_decode.hip: the split-KV merge, reused unchanged
 void sc_attn_combine_launch(int Dh, const float* part, void* out, int ldo, int B, int Sq, int Hq, int nsplit, int o_hs, long o_bs, hipStream_t s);
@@ -22,15 +22,10 @@ __device__ __forceinline__ sc_h8 cvt8(const sc_u2 w, const sc_h2 s) {
 // ------------------------------------------------------------------------------------------------------------------
 // Quantiser and its inverse: 16 lanes per 128-element segment, 8 elements per lane (one 16-byte load, one 8-byte store).
 // ------------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_kv8_quantize(const _Float16* __restrict__ x, int ld, int n, int nseg, uint8_t* __restrict__ cache, int cache_ld,
-                                                      float* __restrict__ scales, int cache_rows, int row0, const int* __restrict__ row0_dev, int x_follows) {
-    const int gid = blockIdx.x * 256 + threadIdx.x, seg = gid >> 4, l = gid & 15;
-    const int r0 = row0_dev ? row0_dev[0] : row0;
-    const int sg = seg < n * nseg ? seg : 0;                  // (lanes past the last segment redo segment 0 and store nothing)
-    const int i = sg / nseg, s = sg - i * nseg, row = r0 + i;
-    const bool live = seg < n * nseg && row >= 0 && row < cache_rows;
-    const int xr = x_follows ? (live ? row : 0) : i;
-    const sc_h8 v = *reinterpret_cast<const sc_h8*>(x + (size_t)xr * (size_t)ld + s * 128 + l * 8);
+// The specification of the header for ONE segment held by 16 consecutive lanes, 8 fp16 values each: the segment's exponent e (every lane gets it)
+// and this lane's 8 codes.  The one text of k_kv8_quantize and k_kv8_rope_qkv_rows.
+struct Kv8Seg { sc_u2 codes; int e; };
+__device__ __forceinline__ Kv8Seg kv8_quantize_seg(const sc_h8 v) {
     float m = 0.f;
 #pragma unroll
     for (int e = 0; e < 8; ++e) m = fmaxf(m, fabsf((float)v[e]));
@@ -47,10 +42,78 @@ __global__ __launch_bounds__(256) void k_kv8_quantize(const _Float16* __restrict
     int p0 = __builtin_amdgcn_cvt_pk_fp8_f32(f[0], f[1], 0, false), p1 = __builtin_amdgcn_cvt_pk_fp8_f32(f[4], f[5], 0, false);
     p0 = __builtin_amdgcn_cvt_pk_fp8_f32(f[2], f[3], p0, true);
     p1 = __builtin_amdgcn_cvt_pk_fp8_f32(f[6], f[7], p1, true);
+    return {sc_u2{(unsigned)p0, (unsigned)p1}, e};
+}
+__device__ __forceinline__ float kv8_scale(int e) { return __uint_as_float((unsigned)(e + 127) << 23); }
+
+__global__ __launch_bounds__(256) void k_kv8_quantize(const _Float16* __restrict__ x, int ld, int n, int nseg, uint8_t* __restrict__ cache, int cache_ld,
+                                                      float* __restrict__ scales, int cache_rows, int row0, const int* __restrict__ row0_dev, int x_follows) {
+    const int gid = blockIdx.x * 256 + threadIdx.x, seg = gid >> 4, l = gid & 15;
+    const int r0 = row0_dev ? row0_dev[0] : row0;
+    const int sg = seg < n * nseg ? seg : 0;                  // (lanes past the last segment redo segment 0 and store nothing)
+    const int i = sg / nseg, s = sg - i * nseg, row = r0 + i;
+    const bool live = seg < n * nseg && row >= 0 && row < cache_rows;
+    const int xr = x_follows ? (live ? row : 0) : i;
+    const Kv8Seg q = kv8_quantize_seg(*reinterpret_cast<const sc_h8*>(x + (size_t)xr * (size_t)ld + s * 128 + l * 8));
     if (live) {
-        *reinterpret_cast<sc_u2*>(cache + (size_t)row * (size_t)cache_ld + s * 128 + l * 8) = sc_u2{(unsigned)p0, (unsigned)p1};
-        if (l == 0) scales[(size_t)row * (size_t)nseg + s] = __uint_as_float((unsigned)(e + 127) << 23);
+        *reinterpret_cast<sc_u2*>(cache + (size_t)row * (size_t)cache_ld + s * 128 + l * 8) = q.codes;
+        if (l == 0) scales[(size_t)row * (size_t)nseg + s] = kv8_scale(q.e);
     }
+}
+
+// sc_kv8_rope_qkv_rows: k_rope_qkv_rows (llm_ops.hip) with the K | V row quantised on the way out.  One 16-lane group per head of the fused
+// q | k | v row of one sequence (Hq + 2 Hkv heads of Dh = 128 fp32 sums), 8 elements per lane.  A rotary pair (j, j + 64) lies inside one head:
+// lanes l and l + 8 load the same a = x[j0 ..], b = x[64 + j0 ..], cos and sin (j0 = (l & 7) * 8); lane l < 8 keeps the first half's
+// fma(-b, sin, a * cos), lane l + 8 the second half's fma(a, sin, b * cos) - k_rope_qkv_rows' fma sequence and ITS rounding to fp16.  q heads are
+// stored as they are; K and V (a cast) heads go through kv8_quantize_seg in registers: the second rounding, of the fp16 value.  So bytes and scales
+// equal sc_rope_qkv_rows_f16 into an fp16 row followed by sc_kv8_quantize_rows of that row, and no fp16 K | V row exists in memory.
+__global__ __launch_bounds__(256) void k_kv8_rope_qkv_rows(const float* __restrict__ x, int ldx, const float* __restrict__ tab_q, const float* __restrict__ tab_k,
+                                                           int tab_rows, const int* __restrict__ pos, int B, int Hq, int Hkv, _Float16* __restrict__ q_out, int ldq,
+                                                           uint8_t* __restrict__ cache, long cache_bs, int cache_ld, float* __restrict__ scales, int cache_rows) {
+    constexpr int DH = 128, HALF = 64;
+    const int heads = Hq + 2 * Hkv;
+    const int gid = blockIdx.x * 256 + threadIdx.x, unit = gid >> 4, l = gid & 15;
+    const bool live = unit < B * heads;
+    const int u = live ? unit : 0;                            // (groups past the last head redo head 0 and store nothing: the shuffles need every lane)
+    const int b = u / heads, h = u - b * heads;
+    const float* xr = x + (size_t)b * (size_t)ldx + h * DH;
+    int p = pos[b];
+    const int prow = p < 0 ? 0 : (p >= cache_rows ? cache_rows - 1 : p);           // device-side positions are clamped (cache row and table row), as k_rope_qkv_rows
+    p = p < 0 ? 0 : (p >= tab_rows ? tab_rows - 1 : p);
+    sc_h8 o;
+    if (h < Hq + Hkv) {
+        const int j0 = (l & 7) * 8;
+        const float* t = (h < Hq ? tab_q : tab_k) + (size_t)p * DH;
+#pragma unroll
+        for (int w = 0; w < 2; ++w) {
+            const sc_f4 a = *reinterpret_cast<const sc_f4*>(xr + j0 + w * 4), bb = *reinterpret_cast<const sc_f4*>(xr + HALF + j0 + w * 4);
+            const sc_f4 cs = *reinterpret_cast<const sc_f4*>(t + j0 + w * 4), sn = *reinterpret_cast<const sc_f4*>(t + HALF + j0 + w * 4);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                float ra = __builtin_fmaf(-bb[e], sn[e], a[e] * cs[e]), rb = __builtin_fmaf(a[e], sn[e], bb[e] * cs[e]);
+                asm volatile("" : "+v"(ra), "+v"(rb));                  // fp32 fma, THEN the fp16 rounding (see k_rope_f32in)
+                o[w * 4 + e] = (_Float16)(l < 8 ? ra : rb);
+            }
+        }
+    } else {
+#pragma unroll
+        for (int w = 0; w < 2; ++w) {
+            const sc_f4 v = *reinterpret_cast<const sc_f4*>(xr + l * 8 + w * 4);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) o[w * 4 + e] = (_Float16)v[e];
+        }
+    }
+    const Kv8Seg q = kv8_quantize_seg(o);                     // (every lane: q heads take part in the shuffles and drop the result)
+    if (!live) return;
+    if (h < Hq) {
+        _Float16* qo = q_out + (size_t)b * (size_t)ldq + h * DH + l * 8;
+        *reinterpret_cast<sc_h4*>(qo) = sc_h4{o[0], o[1], o[2], o[3]};
+        *reinterpret_cast<sc_h4*>(qo + 4) = sc_h4{o[4], o[5], o[6], o[7]};
+        return;
+    }
+    const int s = h - Hq;
+    *reinterpret_cast<sc_u2*>(cache + (size_t)b * (size_t)cache_bs + (size_t)prow * (size_t)cache_ld + s * DH + l * 8) = q.codes;
+    if (l == 0) scales[((size_t)b * (size_t)cache_rows + (size_t)prow) * (size_t)(2 * Hkv) + s] = kv8_scale(q.e);
 }
 
 __global__ __launch_bounds__(256) void k_kv8_dequantize(const uint8_t* __restrict__ cache, int cache_ld, const float* __restrict__ scales, int row0, int n, int nseg,
@@ -85,7 +148,8 @@ constexpr int WAVE_LDS8 = DEC8_PD * (2 * KB8 + SCB) + VST;
 
 __global__ __launch_bounds__(64 * DEC_NW) void k_attn_kv8(const _Float16* __restrict__ Q, int ldq, const uint8_t* __restrict__ cache, int ldc,
                                                            const float* __restrict__ scales, int Sq, int Skv, int Hkv, float scale_log2,
-                                                           const int* __restrict__ kv_len, float* __restrict__ part, int nsplit, int q_hs) {
+                                                           const int* __restrict__ kv_len, float* __restrict__ part, int nsplit, int q_hs, long q_bs,
+                                                           long cache_bs) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     constexpr int DH = 128, DS = 4, DB = 8, VROW = DEC_VROW;
     constexpr int CNT_K = 9 * DEC8_PD - 5, CNT_V = 9 * DEC8_PD - 4;                 // vm ops younger than K(c) / than V(c) at their waits
@@ -93,16 +157,18 @@ __global__ __launch_bounds__(64 * DEC_NW) void k_attn_kv8(const _Float16* __rest
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int rl = lane & 15, g = lane >> 4;
-    const int split = blockIdx.x, h = blockIdx.y;
-    const int kv_valid = kv_len ? min(max(kv_len[0], 0), Skv) : Skv;
+    const int split = blockIdx.x, h = blockIdx.y, b = blockIdx.z;                       // grid = (split, KV head, sequence), as k_attn_decode
+    const int kv_valid = kv_len ? min(max(kv_len[b], 0), Skv) : Skv;
     const DecRange wr = dec_range<DEC_NW_LOG>(kv_valid, nsplit, split, wave);
     const int c_lo = wr.c_lo, c_hi = wr.c_hi, row_end = wr.row_end;                     // (plain ints: the issue lambdas capture them)
     sc_u4 qf[DS];
-    dec_load_q(Q + h * q_hs, ldq, Sq, rl, g, qf);
+    dec_load_q(Q + (size_t)b * (size_t)q_bs + h * q_hs, ldq, Sq, rl, g, qf);
     const int nseg = 2 * Hkv;
-    const uint8_t* kbase = cache + h * DH;
-    const uint8_t* vbase = cache + (Hkv + h) * DH;
-    const float* sbase = scales + h;
+    // sequence b's slice goes into the 64-bit BASE of the three buffer resources; offsets and extents below stay 32-bit and per sequence, so the
+    // rows behind kv_len[b], the row pad and the next sequence's rows are all outside a wave's extent
+    const uint8_t* kbase = cache + (size_t)b * (size_t)cache_bs + h * DH;
+    const uint8_t* vbase = kbase + Hkv * DH;
+    const float* sbase = scales + (size_t)b * (size_t)Skv * (size_t)nseg + h;
     const bool any = c_lo < c_hi && row_end > 0;
     const int b_ext = any ? (int)((unsigned)(row_end - 1) * (unsigned)ldc + DH) : 0;                       // K and V bytes (from kbase / vbase)
     const int s_ext = any ? (int)(((unsigned)(row_end - 1) * (unsigned)nseg + (unsigned)Hkv + 1u) * 4u) : 0;   // scales (from sbase)
@@ -207,7 +273,7 @@ __global__ __launch_bounds__(64 * DEC_NW) void k_attn_kv8(const _Float16* __rest
         }
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");       // no LDS-DMA may still be in flight when the merge reuses the rings / the block ends
-    dec_merge_waves<DEC_NW, DH>(smem, o, m_run, l_run, tid, wave, rl, g, Sq, part + (((size_t)h * Sq) * nsplit + split) * (DH + 2), nsplit);
+    dec_merge_waves<DEC_NW, DH>(smem, o, m_run, l_run, tid, wave, rl, g, Sq, part + ((((size_t)b * Hkv + h) * Sq) * nsplit + split) * (DH + 2), nsplit);
 }
 
 }  // namespace
@@ -251,29 +317,71 @@ extern "C" int sc_kv8_dequantize_rows(const uint8_t* cache, int cache_ld, const 
     return SC_OK;
 }
 
-extern "C" int sc_attention_kv8(const void* q, int ldq, const uint8_t* cache, int cache_ld, const float* scales, void* out, int ldo, int Sq, int Skv,
-                                int kv_heads, int Dh, float scale, int flags, const int32_t* kv_len, int nsplit, void* ws, size_t ws_bytes,
-                                int q_head_stride, int o_head_stride, sc_stream_t stream) {
-    SC_REQUIRE(q && cache && scales && out, "sc_attention_kv8: null pointer argument");
-    SC_KV8_DH("sc_attention_kv8");
-    SC_REQUIRE((flags & ~SC_ATTN_Q_PRESCALED) == 0, "sc_attention_kv8: flags must be 0 or SC_ATTN_Q_PRESCALED (the kernel is non-causal)");
-    SC_REQUIRE(Sq > 0 && Sq <= 16 && Skv > 0 && kv_heads > 0 && kv_heads <= 65535, "sc_attention_kv8: bad sizes (1 <= Sq <= 16 query rows per KV head)");
-    SC_REQUIRE(cache_ld >= 2 * kv_heads * Dh && cache_ld % 16 == 0 && (long)Skv * cache_ld < (1L << 31), "sc_attention_kv8: cache row stride must be a multiple of 16, at least 2 * kv_heads * Dh, the cache below 2 GiB");
-    SC_REQUIRE(ldq % 8 == 0 && ldo % 4 == 0, "sc_attention_kv8: leading dims must be multiples of 8 (out: 4)");
-    SC_REQUIRE(((reinterpret_cast<uintptr_t>(q) | reinterpret_cast<uintptr_t>(cache)) & 15) == 0 && (reinterpret_cast<uintptr_t>(scales) & 3) == 0 &&
-                   (reinterpret_cast<uintptr_t>(out) & 7) == 0, "sc_attention_kv8: q and cache must be 16-byte aligned, out 8-byte");
-    SC_REQUIRE(nsplit >= 1 && nsplit <= 1024, "sc_attention_kv8: nsplit must be in [1, 1024]");
-    const size_t need = (size_t)kv_heads * Sq * nsplit * (Dh + 2) * sizeof(float);
-    if (!ws || ws_bytes < need) return sc_fail(SC_ERR_WORKSPACE, "sc_attention_kv8: split-KV workspace %zu < required %zu", ws_bytes, need);
+// the one launcher of k_attn_kv8 + the split-KV merge: sc_attention_kv8 is its B = 1 call
+static int kv8_attention(const char* name, const void* q, int ldq, const uint8_t* cache, int cache_ld, int64_t cache_bs, const float* scales, void* out, int ldo,
+                         int B, int Sq, int Skv, int kv_heads, int Dh, float scale, int flags, const int32_t* kv_len, int nsplit, void* ws, size_t ws_bytes,
+                         int q_head_stride, int o_head_stride, int64_t q_batch_stride, int64_t o_batch_stride, sc_stream_t stream) {
+    if (!(q && cache && scales && out)) return sc_fail(SC_ERR_ARG, "%s: null pointer argument", name);
+    if (Dh != 128) return sc_fail(SC_ERR_UNSUPPORTED, "%s: head dim %d unsupported (the fp8 KV cache serves 128 only)", name, Dh);
+    if ((flags & ~SC_ATTN_Q_PRESCALED) != 0) return sc_fail(SC_ERR_ARG, "%s: flags must be 0 or SC_ATTN_Q_PRESCALED (the kernel is non-causal)", name);
+    if (!(B > 0 && B <= 65535 && Sq > 0 && Sq <= 16 && Skv > 0 && kv_heads > 0 && kv_heads <= 65535))
+        return sc_fail(SC_ERR_ARG, "%s: bad sizes (1 <= Sq <= 16 query rows per KV head, at most 65535 sequences and KV heads)", name);
+    if (!(cache_ld >= 2 * kv_heads * Dh && cache_ld % 16 == 0 && (long)Skv * cache_ld < (1L << 31)))
+        return sc_fail(SC_ERR_ARG, "%s: cache row stride must be a multiple of 16, at least 2 * kv_heads * Dh, one sequence's cache below 2 GiB", name);
+    if (B > 1 && !(cache_bs % 16 == 0 && cache_bs >= (int64_t)Skv * cache_ld))
+        return sc_fail(SC_ERR_ARG, "%s: cache batch stride (bytes) must be a multiple of 16, at least Skv * cache_ld", name);
+    if (!(ldq % 8 == 0 && ldo % 4 == 0)) return sc_fail(SC_ERR_ARG, "%s: leading dims must be multiples of 8 (out: 4)", name);
+    if (!(((reinterpret_cast<uintptr_t>(q) | reinterpret_cast<uintptr_t>(cache)) & 15) == 0 && (reinterpret_cast<uintptr_t>(scales) & 3) == 0 &&
+          (reinterpret_cast<uintptr_t>(out) & 7) == 0))
+        return sc_fail(SC_ERR_ARG, "%s: q and cache must be 16-byte aligned, out 8-byte", name);
+    if (!(nsplit >= 1 && nsplit <= 1024)) return sc_fail(SC_ERR_ARG, "%s: nsplit must be in [1, 1024]", name);
+    const size_t need = (size_t)B * kv_heads * Sq * nsplit * (Dh + 2) * sizeof(float);
+    if (!ws || ws_bytes < need) return sc_fail(SC_ERR_WORKSPACE, "%s: split-KV workspace %zu < required %zu", name, ws_bytes, need);
     const int qhs = q_head_stride > 0 ? q_head_stride : Dh, ohs = o_head_stride > 0 ? o_head_stride : Dh;
-    SC_REQUIRE(qhs % 8 == 0 && ohs % 4 == 0, "sc_attention_kv8: head strides must be multiples of 8 (q) / 4 (out)");
+    const long qbs = q_batch_stride > 0 ? (long)q_batch_stride : (long)Sq * ldq, obs = o_batch_stride > 0 ? (long)o_batch_stride : (long)Sq * ldo;
+    if (!(qhs % 8 == 0 && ohs % 4 == 0 && qbs % 8 == 0 && obs % 4 == 0))
+        return sc_fail(SC_ERR_ARG, "%s: head and batch strides must be multiples of 8 (q) / 4 (out)", name);
     hipStream_t s = (hipStream_t)stream;
     const float sl2 = (flags & SC_ATTN_Q_PRESCALED) ? 1.0f : scale * 1.4426950408889634f;
     constexpr int LDS = dec_lds_bytes(DEC_NW * WAVE_LDS8);
     sc_set_max_lds<k_attn_kv8>(LDS);
-    hipLaunchKernelGGL(k_attn_kv8, dim3((unsigned)nsplit, (unsigned)kv_heads), dim3(64 * DEC_NW), LDS, s, (const _Float16*)q, ldq, cache, cache_ld, scales, Sq, Skv,
-                       kv_heads, sl2, kv_len, (float*)ws, nsplit, qhs);
-    sc_attn_combine_launch(128, (const float*)ws, out, ldo, 1, Sq, kv_heads, nsplit, ohs, (long)Sq * ldo, s);
-    SC_CHECK_LAUNCH("sc_attention_kv8");
+    hipLaunchKernelGGL(k_attn_kv8, dim3((unsigned)nsplit, (unsigned)kv_heads, (unsigned)B), dim3(64 * DEC_NW), LDS, s, (const _Float16*)q, ldq, cache, cache_ld, scales,
+                       Sq, Skv, kv_heads, sl2, kv_len, (float*)ws, nsplit, qhs, qbs, (long)(B > 1 ? cache_bs : 0));
+    sc_attn_combine_launch(128, (const float*)ws, out, ldo, B, Sq, kv_heads, nsplit, ohs, obs, s);
+    SC_CHECK_LAUNCH(name);
+    return SC_OK;
+}
+
+extern "C" int sc_attention_kv8(const void* q, int ldq, const uint8_t* cache, int cache_ld, const float* scales, void* out, int ldo, int Sq, int Skv,
+                                int kv_heads, int Dh, float scale, int flags, const int32_t* kv_len, int nsplit, void* ws, size_t ws_bytes,
+                                int q_head_stride, int o_head_stride, sc_stream_t stream) {
+    return kv8_attention("sc_attention_kv8", q, ldq, cache, cache_ld, 0, scales, out, ldo, 1, Sq, Skv, kv_heads, Dh, scale, flags, kv_len, nsplit, ws, ws_bytes,
+                         q_head_stride, o_head_stride, 0, 0, stream);
+}
+
+extern "C" int sc_attention_kv8_batched(const void* q, int ldq, const uint8_t* cache, int cache_ld, int64_t cache_batch_stride, const float* scales, void* out,
+                                        int ldo, int B, int Sq, int Skv, int kv_heads, int Dh, float scale, int flags, const int32_t* kv_len, int nsplit, void* ws,
+                                        size_t ws_bytes, int q_head_stride, int o_head_stride, int64_t q_batch_stride, int64_t o_batch_stride, sc_stream_t stream) {
+    return kv8_attention("sc_attention_kv8_batched", q, ldq, cache, cache_ld, cache_batch_stride, scales, out, ldo, B, Sq, Skv, kv_heads, Dh, scale, flags, kv_len,
+                         nsplit, ws, ws_bytes, q_head_stride, o_head_stride, q_batch_stride, o_batch_stride, stream);
+}
+
+extern "C" int sc_kv8_rope_qkv_rows(const float* x, int ldx, const float* tab_q, const float* tab_k, int tab_rows, const int32_t* positions, int B, int q_heads,
+                                    int kv_heads, int Dh, void* q_out, int ldq, uint8_t* cache, int64_t cache_batch_stride, int cache_ld, float* scales,
+                                    int cache_rows, sc_stream_t stream) {
+    SC_REQUIRE(x && tab_q && tab_k && positions && q_out && cache && scales, "sc_kv8_rope_qkv_rows: null pointer argument");
+    SC_KV8_DH("sc_kv8_rope_qkv_rows");
+    SC_REQUIRE(B > 0 && q_heads > 0 && kv_heads > 0 && tab_rows > 0 && cache_rows > 0, "sc_kv8_rope_qkv_rows: bad sizes");
+    SC_REQUIRE(ldx >= (q_heads + 2 * kv_heads) * Dh && ldx % 4 == 0 && ldq >= q_heads * Dh && ldq % 4 == 0 && cache_ld >= 2 * kv_heads * Dh && cache_ld % 8 == 0 &&
+               cache_batch_stride % 8 == 0 && (B == 1 || cache_batch_stride >= (int64_t)cache_rows * cache_ld),
+               "sc_kv8_rope_qkv_rows: leading dimensions too small or not multiples of 4 (x, q_out) / 8 (cache row and batch stride, in bytes)");
+    SC_REQUIRE(((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(tab_q) | reinterpret_cast<uintptr_t>(tab_k)) & 15) == 0 &&
+               ((reinterpret_cast<uintptr_t>(q_out) | reinterpret_cast<uintptr_t>(cache)) & 7) == 0 && (reinterpret_cast<uintptr_t>(scales) & 3) == 0,
+               "sc_kv8_rope_qkv_rows: x / tables must be 16-byte aligned, q_out and cache 8-byte, scales 4-byte");
+    const long lanes = (long)B * (q_heads + 2 * kv_heads) * 16;
+    SC_REQUIRE(lanes <= (1L << 30), "sc_kv8_rope_qkv_rows: too many heads for one launch");
+    hipLaunchKernelGGL(k_kv8_rope_qkv_rows, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, (hipStream_t)stream, x, ldx, tab_q, tab_k, tab_rows, positions, B,
+                       q_heads, kv_heads, (_Float16*)q_out, ldq, cache, (long)cache_batch_stride, cache_ld, scales, cache_rows);
+    SC_CHECK_LAUNCH("sc_kv8_rope_qkv_rows");
     return SC_OK;
 }

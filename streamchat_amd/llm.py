@@ -65,14 +65,23 @@ DEFAULT_DECODE_WEIGHTS = check_decode_weights(os.environ.get("SC_DECODE_WEIGHTS"
 KV_CACHE = ("fp16", "fp8")
 
 
-def check_kv_cache(v):
+def check_kv_cache(v, name="kv_cache"):
     if v not in KV_CACHE:
-        raise ValueError(f"kv_cache must be one of {KV_CACHE}, got {v!r}")
+        raise ValueError(f"{name} must be one of {KV_CACHE}, got {v!r}")
     return v
 
 
 # SC_KV_CACHE=fp8: what Qwen2Model(kv_cache=None) means in this process (read once; the constructor argument wins)
 DEFAULT_KV_CACHE = check_kv_cache(os.environ.get("SC_KV_CACHE") or "fp16")
+
+
+def check_batch_kv_cache(v):
+    return check_kv_cache(v, "batch_kv_cache")
+
+
+# SC_BATCH_KV_CACHE=fp8: what Qwen2Model(batch_kv_cache=None) means in this process - the cache format of the BatchDecoders built on the model
+# (chunk captions, beam search).  Read once; the constructor argument wins.  Deliberately independent of SC_KV_CACHE / kv_cache.
+DEFAULT_BATCH_KV_CACHE = check_batch_kv_cache(os.environ.get("SC_BATCH_KV_CACHE") or "fp16")
 
 
 # a layer's decode projections and, in Qwen2Model.w8["L"][l], the key of each one's per-row scales
@@ -92,10 +101,12 @@ def _h(t, device):
 class Qwen2Model:
     """Decoder stack + lm_head on the HIP kernels, with a contiguous per-layer KV cache [max_seq, 2*Hkv*Dh] (K | V)."""
 
-    def __init__(self, state_dict, cfg: Qwen2ConfigLite, device="cuda", max_seq=65536, consume=False, trim_last_layer=True, decode_weights=None, kv_cache=None):
+    def __init__(self, state_dict, cfg: Qwen2ConfigLite, device="cuda", max_seq=65536, consume=False, trim_last_layer=True, decode_weights=None, kv_cache=None,
+                 batch_kv_cache=None):
         self.cfg, self.device, self.max_seq = cfg, torch.device(device), max_seq
         self.kv_cache, self.kv8, self._kv_stage = "fp16", None, None
         self.set_kv_cache(kv_cache if kv_cache is not None else DEFAULT_KV_CACHE)
+        self.set_batch_kv_cache(batch_kv_cache if batch_kv_cache is not None else DEFAULT_BATCH_KV_CACHE)
         decode_weights = check_decode_weights(decode_weights if decode_weights is not None else DEFAULT_DECODE_WEIGHTS)
         self.w8 = None                              # enable_fp8_decode(): the e4m3 copies of the decode projections THIS object decodes from
         self._w8_shared = {}                        # ... which every shared_view() of these weights shares (quantised once, whoever asks first)
@@ -163,18 +174,31 @@ class Qwen2Model:
         (bytes [max_seq, 2 Hkv Dh (+ pad)], scales [max_seq, 2 Hkv]); `self.cache[l]` is then, for EVERY layer, ONE fp16 staging buffer
         [max_seq, 2 Hkv Dh (+ pad)]: the unchanged prefill and q/k/v kernels write fp16 rows into it and read the fp16 attention's operands from
         it, and each layer moves its rows into its own fp8 cache before the next layer reuses the buffer.  Drops the cache this object holds.
-        A shared_view() inherits the mode and owns its cache; BatchDecoder keeps fp16 caches of its own.  Also: Qwen2Model(..., kv_cache="fp8"),
-        SC_KV_CACHE=fp8.
+        A shared_view() inherits the mode and owns its cache.  BatchDecoder owns its caches and takes their format from `batch_kv_cache`
+        (set_batch_kv_cache), NOT from this mode: fp16 unless asked.  Also: Qwen2Model(..., kv_cache="fp8"), SC_KV_CACHE=fp8.
 
         Invariant: while `kv_cache == "fp8"`, `cache[l] is _kv_stage` for every layer and `kv8` holds the rows.  forward() and the decode body
-        test the STRING only.  One place relies on that: BatchDecoder's per-sequence prefill lends the model its own fp16 caches and runs it
-        with the string set to "fp16" (plain assignment, saved and restored with `cache`), leaving `kv8` / `_kv_stage` where they are.  Calling
-        this method there instead would drop the fp8 cache."""
+        test the STRING only.  One place relies on that: BatchDecoder's per-sequence prefill lends the model its own caches and runs it with the
+        string set to the DECODER's mode (plain assignment, saved and restored with `cache`, `kv8` and `_kv_stage`; an fp16 decoder leaves the last
+        two where they are, an fp8 one points them at its slices and its staging buffer).  Calling this method there instead would drop the fp8 cache."""
         mode = check_kv_cache(mode)
         if mode == "fp8" and self.cfg.head_dim != 128:
             raise ValueError(f"kv_cache='fp8' needs head_dim 128, got {self.cfg.head_dim}")
         if mode != self.kv_cache:
             self.kv_cache, self.kv8, self._kv_stage, self.cache, self.cache_len, self._nsplit_prompt = mode, None, None, None, 0, None
+        return self
+
+    def set_batch_kv_cache(self, mode):
+        """"fp8": BatchDecoders built on this object (the chunk captions of a product step, every beam search) keep e4m3 caches in the format of
+        set_kv_cache - per layer uint8 [B, cap, 2 Hkv Dh] with fp32 scales [B, cap, 2 Hkv] (include/streamchat_hip_kv8_batched.h): K/V is about
+        70 % of the bytes of that step at the product shape, and the caches take 0.516 of the memory.  OPT-IN, the same accuracy trade (about
+        2.65 % relative rms error per segment; captions and beams may differ from an fp16 run), and deliberately NOT derived from `kv_cache`: an
+        fp8-cache model's BatchDecoder keeps producing the fp16-cache tokens unless asked.  A shared_view() inherits it; BatchDecoder(kv_cache=...)
+        overrides it per decoder.  Also: Qwen2Model(..., batch_kv_cache="fp8"), SC_BATCH_KV_CACHE=fp8."""
+        mode = check_batch_kv_cache(mode)
+        if mode == "fp8" and self.cfg.head_dim != 128:
+            raise ValueError(f"batch_kv_cache='fp8' needs head_dim 128, got {self.cfg.head_dim}")
+        self.batch_kv_cache = mode
         return self
 
     def embed_tokens(self, ids):
@@ -673,12 +697,23 @@ class BatchDecoder:
     without a KV cache, utiles.py:539-559).  Each sequence is prefilled on its own (prefill is compute-bound, batching buys nothing)
     into slice b of ONE per-layer cache [B, cap, 2*dkv]; decode then advances all B sequences per step: the projections are GEMMs
     with M = B, so the 15 GB of weights stream once per step instead of once per sequence, the new K/V rows are scattered with one
-    index_copy per layer, and attention is ONE launch per layer over the batch (per-sequence kv_len, split-KV)."""
+    index_copy per layer, and attention is ONE launch per layer over the batch (per-sequence kv_len, split-KV).
 
-    def __init__(self, lm, prompts, max_new_tokens, replicate=None):
+    The caches are this object's own: fp16 `self.cache[l]` [B, cap, 2*dkv], or with kv_cache="fp8" `self.kv8[l]` = (e4m3 bytes uint8 [B, cap, 2*dkv],
+    scales fp32 [B, cap, 2*Hkv]) in the format of Qwen2Model.set_kv_cache - the step then appends with ops.kv8_rope_qkv_rows and attends with
+    ops.attention_kv8_batched, everything else is the one body.  An accuracy trade, so opt-in: see Qwen2Model.set_batch_kv_cache."""
+
+    kv_cache, kv8 = "fp16", None        # (class defaults: the mode of an object that __init__ has not set up, as tests/_attn_cases.py builds one)
+
+    def __init__(self, lm, prompts, max_new_tokens, replicate=None, kv_cache=None):
         """prompts: list of [n_b, H] fp16 embeddings (image rows already spliced).  `replicate=N` (beam search): ONE prompt, prefilled once,
-        its cache rows copied into N slots - the N beams of llm.LlavaQwenForCausalLM's beam search start from the same prompt."""
+        its cache rows copied into N slots - the N beams of llm.LlavaQwenForCausalLM's beam search start from the same prompt.
+        kv_cache: "fp16" | "fp8", None = lm.batch_kv_cache (NOT lm.kv_cache)."""
         c = lm.cfg
+        self.kv_cache = check_batch_kv_cache(kv_cache if kv_cache is not None else lm.batch_kv_cache)
+        if self.kv_cache == "fp8" and c.head_dim != 128:
+            raise ValueError(f"BatchDecoder(kv_cache='fp8') needs head_dim 128, got {c.head_dim}")
+        fp8 = self.kv_cache == "fp8"
         if replicate is not None:
             if len(prompts) != 1:
                 raise ValueError("BatchDecoder(replicate=N) takes exactly one prompt")
@@ -691,26 +726,36 @@ class BatchDecoder:
         self._rope_tabs = lm.rope_tabs(self.cap)                 # rotary tables cover every position of this batch before a step is captured; the
                                                                  # reference held here keeps them alive if the process-wide cache regrows
         # (dense rows here: padded rows - KV_ROW_PAD - measured no gain on the batched step, 10.64 / 10.68 against 10.67 / 10.73 ms: 26 streams at 26 bases)
-        self.cache = [torch.empty((self.B, self.cap, 2 * c.kv_heads * c.head_dim), dtype=torch.float16, device=dev) for _ in range(c.layers)]
+        w = 2 * c.kv_heads * c.head_dim
+        e = lambda shape, dt: torch.empty(shape, dtype=dt, device=dev)
+        self.cache = None if fp8 else [e((self.B, self.cap, w), torch.float16) for _ in range(c.layers)]
+        self.kv8 = [(e((self.B, self.cap, w), torch.uint8), e((self.B, self.cap, 2 * c.kv_heads), torch.float32)) for _ in range(c.layers)] if fp8 else None
+        stage = e((self.cap, w), torch.float16) if fp8 else None      # ONE fp16 staging buffer for the prefills (Qwen2Model.forward's fp8 path)
         self.len = torch.zeros(self.B, dtype=torch.int32, device=dev)
         self._ws_pick = torch.empty(max(ops.sample_token_workspace_bytes(self.B), 256), dtype=torch.uint8, device=dev)      # owned: the decode step is graph-captured
         first_logits = []
         # (forward() also records the split-KV factor of "the prompt in the cache": it belongs to the saved state - ADVICE r04 - or an eager
         #  decode that continues the earlier prompt would merge its partials in another grouping than a DecodeGraph built for it)
-        # (the per-sequence prefill below writes THIS object's fp16 caches: on an fp8-cache model it runs in fp16 mode.  The mode STRING is
-        #  assigned, not set_kv_cache(): that would drop lm.kv8 - see the invariant in its docstring)
-        saved = (lm.cache, lm.cache_len, lm.max_seq, lm._nsplit_prompt, lm.kv_cache)
+        # (the per-sequence prefill below writes THIS object's caches through Qwen2Model.forward in THIS object's mode, whatever the model's own
+        #  is: fp16 - the model is lent slice b of every layer's cache; fp8 - forward's fp8 path, with lm.kv8 pointed at slice b's bytes and scales
+        #  and lm.cache / lm._kv_stage at the staging buffer.  The mode STRING is assigned, not set_kv_cache(): that would drop lm.kv8 - see the
+        #  invariant in its docstring.  The model's own cache, fp8 rows and staging buffer are saved and come back untouched.)
+        saved = (lm.cache, lm.cache_len, lm.max_seq, lm._nsplit_prompt, lm.kv_cache, lm.kv8, lm._kv_stage)
         try:
-            lm.kv_cache = "fp16"
-            for b, e in enumerate(prompts):
-                lm.cache, lm.cache_len, lm.max_seq = [cl[b] for cl in self.cache], 0, self.cap
-                first_logits.append(lm.forward(e.to(dev)))
+            lm.kv_cache = self.kv_cache
+            for b, emb in enumerate(prompts):
+                if fp8:
+                    lm.kv8, lm._kv_stage, lm.cache = [(kb[b], ks[b]) for kb, ks in self.kv8], stage, [stage] * c.layers
+                else:
+                    lm.cache = [cl[b] for cl in self.cache]
+                lm.cache_len, lm.max_seq = 0, self.cap
+                first_logits.append(lm.forward(emb.to(dev)))
                 self.len[b] = lm.cache_len
         finally:
-            lm.cache, lm.cache_len, lm.max_seq, lm._nsplit_prompt, lm.kv_cache = saved
-        if replicate is not None:                      # slot 0 holds the prompt: the other beams get its K / V rows and its logits
+            lm.cache, lm.cache_len, lm.max_seq, lm._nsplit_prompt, lm.kv_cache, lm.kv8, lm._kv_stage = saved
+        if replicate is not None:                      # slot 0 holds the prompt: the other beams get its K / V rows (bytes AND scales) and its logits
             n0 = int(self.len[0].item())
-            for cl in self.cache:
+            for cl in self._cache_tensors():
                 cl[1:, :n0].copy_(cl[0:1, :n0].expand(self.B - 1, -1, -1))
             self.len.fill_(n0)
             first_logits = first_logits * self.B
@@ -718,6 +763,10 @@ class BatchDecoder:
         self._qkv32 = torch.empty((self.B, (c.heads + 2 * c.kv_heads) * c.head_dim), dtype=torch.float32, device=dev)
         self._q16 = torch.empty((self.B, c.heads * c.head_dim), dtype=torch.float16, device=dev)
         self.logits = torch.stack(first_logits)                                  # [B, vocab] fp32
+
+    def _cache_tensors(self):
+        """every [B, cap, *] tensor that holds rows of the sequences: the fp16 caches, or the e4m3 bytes and their scales"""
+        return self.cache if self.kv_cache != "fp8" else [t for pair in self.kv8 for t in pair]
 
     def step(self, tokens):
         """tokens [B] int32 (device) -> logits [B, vocab] fp32 for the next position of every sequence.  Everything that changes from
@@ -733,13 +782,19 @@ class BatchDecoder:
             # cache, in ONE launch (round 5: was rope(q) + rope(k|v) + index_copy_)
             s32 = ops.gemm(x, L["wqkv"], L["bqkv"], out=self._qkv32, out_f32=True)
             tq, tk = self._rope_tabs
-            ck = self.cache[l]
-            q = ops.rope_qkv_rows(s32, tq, tk, self.len, c.heads, c.kv_heads, Dh, self._q16, ck)
             # the G query heads of a KV group as G query ROWS of that KV head (addressing only; q batch stride = dq)
             G = c.heads // c.kv_heads
-            att = ops.attention(q.as_strided((B, G, Dh), (dq, Dh, 1)), ck[:, :, :dkv], ck[:, :, dkv:], c.kv_heads, c.kv_heads, Dh, Dh ** -0.5,
-                                causal=False, kv_len=kvlen, nsplit=self.nsplit, q_head_stride=G * Dh, o_head_stride=G * Dh, out_ld=Dh,
-                                ws=self._ws_attn, q_prescaled=True).view(B, dq)
+            if self.kv_cache == "fp8":      # the new row is quantised on the way into the cache and attended from its quantised form, as the others
+                kb, ks = self.kv8[l]
+                q = ops.kv8_rope_qkv_rows(s32, tq, tk, self.len, c.heads, c.kv_heads, Dh, self._q16, kb, ks)
+                att = ops.attention_kv8_batched(q.as_strided((B, G, Dh), (dq, Dh, 1)), kb, ks, c.kv_heads, Dh, Dh ** -0.5, kv_len=kvlen, nsplit=self.nsplit,
+                                                q_head_stride=G * Dh, o_head_stride=G * Dh, out_ld=Dh, ws=self._ws_attn, q_prescaled=True).view(B, dq)
+            else:
+                ck = self.cache[l]
+                q = ops.rope_qkv_rows(s32, tq, tk, self.len, c.heads, c.kv_heads, Dh, self._q16, ck)
+                att = ops.attention(q.as_strided((B, G, Dh), (dq, Dh, 1)), ck[:, :, :dkv], ck[:, :, dkv:], c.kv_heads, c.kv_heads, Dh, Dh ** -0.5,
+                                    causal=False, kv_len=kvlen, nsplit=self.nsplit, q_head_stride=G * Dh, o_head_stride=G * Dh, out_ld=Dh,
+                                    ws=self._ws_attn, q_prescaled=True).view(B, dq)
             h2 = ops.gemm(att, L["wo"], None, residual=h)
             m = ops.gemm(ops.rmsnorm(h2, L["ln2"], c.eps), L["wgu"], None, epilogue="swiglu")
             h = ops.gemm(m, L["wd"], None, residual=h2)
@@ -751,8 +806,10 @@ class BatchDecoder:
         B, dev, c = self.B, self.lm.device, self.lm.cfg
         longest = int(self.len.max().item()) + max_new_tokens
         self.nsplit = getattr(self, "nsplit_override", None) or batched_decode_nsplit(B, c.kv_heads, longest)
-        self._ws_attn = torch.empty(max(ops.attention_workspace_bytes(B, c.kv_heads, c.heads // c.kv_heads, self.nsplit, c.head_dim), 256),
-                                    dtype=torch.uint8, device=dev)
+        # (the e4m3 kernel leaves partials at one split too: the same size formula without the nsplit == 1 shortcut)
+        need = (ops.attention_workspace_bytes(B, c.kv_heads, c.heads // c.kv_heads, self.nsplit, c.head_dim) if self.kv_cache != "fp8" or self.nsplit > 1
+                else B * c.heads * (c.head_dim + 2) * 4)
+        self._ws_attn = torch.empty(max(need, 256), dtype=torch.uint8, device=dev)
 
     def reorder(self, beam_idx):
         """slot b continues the sequence that slot beam_idx[b] held (HF `reorder_cache`): the used rows of every layer's cache are gathered"""
@@ -760,7 +817,7 @@ class BatchDecoder:
         if bool((idx.cpu() == torch.arange(self.B)).all()):
             return
         n = int(self.len.max().item())
-        for cl in self.cache:
+        for cl in self._cache_tensors():
             cl[:, :n].copy_(cl[:, :n].index_select(0, idx))
         self.len.copy_(self.len.index_select(0, idx))
 

@@ -928,6 +928,77 @@ def attention_kv8(q, cache, scales, kv_heads: int, Dh: int, scale: float, kv_len
     return out
 
 
+def _kv8_batch_operands(cache, scales, kv_heads, Dh, what):
+    """the batched decoder's cache: uint8 [B, cap, >= 2 * kv_heads * Dh] with unit last stride and a dense batch stride, scales fp32 [B, cap, 2 * kv_heads]"""
+    if (cache.dtype != torch.uint8 or scales.dtype != torch.float32 or cache.dim() != 3 or cache.stride(2) != 1 or cache.shape[2] < 2 * kv_heads * Dh
+            or cache.stride(0) != cache.shape[1] * cache.stride(1) or not scales.is_contiguous() or scales.shape != (cache.shape[0], cache.shape[1], 2 * kv_heads)):
+        raise StreamChatHipError(f"{what}: the cache must be e4m3 bytes (uint8 [B, cap, >= 2 * kv_heads * Dh], unit last stride, dense batch stride) with "
+                                 "contiguous fp32 scales [B, cap, 2 * kv_heads]")
+
+
+def kv8_rope_qkv_rows(x32, tab_q, tab_k, positions, q_heads: int, kv_heads: int, Dh: int, q_out, cache, scales):
+    """`rope_qkv_rows` into an e4m3 cache: x32 [B, (q_heads + 2 kv_heads) * Dh] fp32 -> q_out [B, q_heads * Dh] fp16 (the bits of rope_qkv_rows) and row
+    positions[b] of cache[b] / scales[b] (uint8 [B, cap, 2 * kv_heads * Dh], fp32 [B, cap, 2 * kv_heads]): the rotated K | cast V row rounded to fp16 and
+    quantised (include/streamchat_hip_kv8.h) in ONE launch.  Bit-identical to rope_qkv_rows into an fp16 row + kv8_quantize_rows of it."""
+    _require_cuda(x32, tab_q, tab_k, positions, q_out, cache, scales)
+    _kv8_batch_operands(cache, scales, kv_heads, Dh, "kv8_rope_qkv_rows")
+    if x32.dtype != torch.float32 or q_out.dtype != torch.float16 or positions.dtype != torch.int32 or x32.dim() != 2 or q_out.dim() != 2:
+        raise StreamChatHipError("kv8_rope_qkv_rows: fp32 x [B, *], fp16 q_out [B, *], int32 positions")
+    if (x32.stride(-1) != 1 or q_out.stride(-1) != 1 or tab_q.shape[0] != tab_k.shape[0] or not positions.is_contiguous() or positions.numel() != x32.shape[0]
+            or cache.shape[0] != x32.shape[0] or q_out.shape[0] != x32.shape[0]):
+        raise StreamChatHipError("kv8_rope_qkv_rows: unit last strides, equal table lengths, contiguous positions [B], B rows of x, q_out and cache")
+    from ctypes import c_void_p
+    with torch.cuda.device(x32.device):
+        check(_lib.load().sc_kv8_rope_qkv_rows(c_void_p(x32.data_ptr()), x32.stride(0), c_void_p(tab_q.data_ptr()), c_void_p(tab_k.data_ptr()), int(tab_q.shape[0]),
+                                               ptr(positions), x32.shape[0], q_heads, kv_heads, Dh, c_void_p(q_out.data_ptr()), q_out.stride(0),
+                                               c_void_p(cache.data_ptr()), c_int64(cache.stride(0)), cache.stride(1), ptr(scales), cache.shape[1],
+                                               stream_ptr(x32.device)), "sc_kv8_rope_qkv_rows")
+    return q_out
+
+
+def attention_kv8_batched(q, cache, scales, kv_heads: int, Dh: int, scale: float, kv_len=None, out=None, nsplit: int = 1, q_head_stride: int = 0,
+                          o_head_stride: int = 0, out_ld=None, ws=None, q_prescaled: bool = False):
+    """`attention_kv8` for B sequences in one launch: q [B, Sq <= 16, *] (Sq query rows per KV head), cache uint8 [B, cap, 2 * kv_heads * Dh] with scales
+    [B, cap, 2 * kv_heads], kv_len int32 [B] (None: cap rows each).  For every b bit-identical to attention_kv8 on slice b with the same nsplit, hence
+    to `attention` (batched, same nsplit and kv_len) over the dequantised caches.  Returns [B, Sq, kv_heads * Dh]."""
+    _require_cuda(q, cache, scales)
+    _kv8_batch_operands(cache, scales, kv_heads, Dh, "attention_kv8_batched")
+    if q.dtype != torch.float16 or q.dim() != 3 or q.shape[0] != cache.shape[0] or q.stride(-1) != 1:
+        raise StreamChatHipError("attention_kv8_batched: q must be fp16 [B, Sq, *] with unit last stride, B the cache's")
+    B, Sq, Skv = q.shape[0], q.shape[1], cache.shape[1]
+    # the elements one sequence's q occupies: Sq rows q.stride(1) apart, kv_heads heads of Dh elements a head stride apart
+    span = q.stride(1) * (Sq - 1) + (q_head_stride or Dh) * (kv_heads - 1) + Dh
+    if (not q_head_stride and q.shape[2] < kv_heads * Dh) or (B > 1 and span > q.stride(0)):
+        raise StreamChatHipError("attention_kv8_batched: the kv_heads * Dh query elements of a row do not fit q's rows / batch stride")
+    if out is None:
+        out = torch.empty((B, Sq, kv_heads * Dh), dtype=torch.float16, device=q.device)
+    else:
+        _require_cuda(out)
+        if (out.dtype != torch.float16 or out.device != q.device or out.dim() != 3 or out.stride(-1) != 1 or out.shape[0] != B
+                or out.shape[1] * out.shape[2] < Sq * kv_heads * Dh or (B > 1 and out.stride(0) < Sq * kv_heads * Dh)):
+            raise StreamChatHipError("attention_kv8_batched: out must be fp16 [B, Sq, >= kv_heads * Dh] on q's device with unit last stride")
+    from ctypes import c_void_p
+    P = lambda t: None if t is None else c_void_p(t.data_ptr())
+    ldo = out.stride(1) if out_ld is None else out_ld
+    kl = None
+    if kv_len is not None:
+        _require_cuda(kv_len)
+        if kv_len.dtype != torch.int32 or not kv_len.is_contiguous() or kv_len.numel() != B:
+            raise StreamChatHipError("attention_kv8_batched: kv_len must be a contiguous int32 tensor [B]")
+        kl = kv_len
+    need = B * kv_heads * Sq * nsplit * (Dh + 2) * 4
+    if ws is None:
+        ws = _workspace(need, q.device)
+    elif ws.numel() * ws.element_size() < need:
+        raise StreamChatHipError(f"attention_kv8_batched: workspace {ws.numel() * ws.element_size()} < required {need}")
+    with torch.cuda.device(q.device), _timed("k_attn_kv8", 4.0 * B * kv_heads * Sq * Skv * Dh):
+        check(_lib.load().sc_attention_kv8_batched(P(q), q.stride(1), P(cache), cache.stride(1), c_int64(cache.stride(0)), P(scales), P(out), ldo, B, Sq, Skv, kv_heads,
+                                                   Dh, c_float(scale), 2 if q_prescaled else 0, P(kl), nsplit, P(ws), c_size_t(ws.numel() * ws.element_size()),
+                                                   q_head_stride, o_head_stride, c_int64(q.stride(0)), c_int64(out.stride(0)), stream_ptr(q.device)),
+              "sc_attention_kv8_batched")
+    return out
+
+
 def decode_advance(nxt, ring, cnt, tok, pos, kv_len, nprev):
     """one launch: ring[cnt] = nxt; tok = nxt; cnt, pos, kv_len, nprev += 1 (device scalars of a captured decode step)"""
     _require_cuda(nxt, ring, cnt, tok, pos, kv_len, nprev)
