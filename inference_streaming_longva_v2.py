@@ -99,6 +99,11 @@ def parse_args(argv=None):
                         "fp8 = the e4m3 format of --kv_cache, about half the K/V bytes per step and 0.516 of the caches' memory.  An accuracy trade, off "
                         "by default (~2.65 %% relative rms error per segment; head dim 128 only): captions and beams may differ from an fp16 run.  "
                         "Independent of --kv_cache; a decoding setting like it: not part of the memory fingerprint")
+    p.add_argument("--batch_decode_weights", type=str, choices=["fp16", "fp8"], default="fp16",
+                   help="weights the BATCHED decode of every model of the process streams (the chunk captions of --batch_captions 1, beam search): "
+                        "fp8 = the e4m3 copies of --decode_weights through the skinny e4m3 GEMM, half of the weight bytes per step.  An accuracy "
+                        "trade, off by default (~2.6 %% relative rms error per projection): captions and beams may differ from an fp16 run.  "
+                        "Independent of --decode_weights and --batch_kv_cache; a decoding setting like them: not part of the memory fingerprint")
     args = p.parse_args(argv)
     if args.num_beams != 1 and (args.temperature or 0) > 0:
         # the reference forwards num_beams and do_sample = (temperature > 0) to HF generate (:252-256): with both that is HF's beam SAMPLING, which
@@ -148,6 +153,10 @@ def build_models(args):
         for m in built:
             if isinstance(getattr(m, "lm", None), LM.Qwen2Model):
                 m.lm.set_batch_kv_cache("fp8")
+    if getattr(args, "batch_decode_weights", "fp16") == "fp8":
+        for m in built:
+            if isinstance(getattr(m, "lm", None), LM.Qwen2Model):
+                m.lm.set_batch_decode_weights("fp8")
     return built
 
 

@@ -79,6 +79,12 @@ EXT_SIGNATURES = {
                                      c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p]),
 }
 
+# include/streamchat_hip_w8_batched.h - changelog entry w8-2: the e4m3-weight GEMM of the BATCHED decode step.  Additive, with a table of its own
+# (EXT_SIGNATURES is the symbol set of streamchat_hip_w8.h itself and stays as it is); bound in load() like every other symbol
+W8_BATCHED_SIGNATURES = {
+    "sc_gemm_w8_f16": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
+}
+
 # include/streamchat_hip_kv8.h - FP8 (e4m3) KV cache for batch-1 decode: a second additive extension header with a table of its own (base ABI 9
 # and both tables above are untouched); bound in load() like every other symbol
 KV8_SIGNATURES = {
@@ -130,7 +136,7 @@ def load():
     except ImportError:
         pass
     lib = ctypes.CDLL(LIB_PATH)
-    for name, (res, args) in list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()) + list(KV8_SIGNATURES.items()) + list(KV8_BATCHED_SIGNATURES.items()) + list(TEXT_SIGNATURES.items()):
+    for name, (res, args) in list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()) + list(W8_BATCHED_SIGNATURES.items()) + list(KV8_SIGNATURES.items()) + list(KV8_BATCHED_SIGNATURES.items()) + list(TEXT_SIGNATURES.items()):
         try:
             fn = getattr(lib, name)
         except AttributeError as e:

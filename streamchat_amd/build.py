@@ -17,7 +17,7 @@ def needs_build() -> bool:
         return True
     t = os.path.getmtime(LIB)
     srcs = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".hip", ".h")) or f == "Makefile"]
-    srcs += [os.path.join(HERE, "..", "include", h) for h in ("streamchat_hip.h", "streamchat_hip_w8.h", "streamchat_hip_kv8.h", "streamchat_hip_kv8_batched.h", "streamchat_hip_text.h")]
+    srcs += [os.path.join(HERE, "..", "include", h) for h in ("streamchat_hip.h", "streamchat_hip_w8.h", "streamchat_hip_w8_batched.h", "streamchat_hip_kv8.h", "streamchat_hip_kv8_batched.h", "streamchat_hip_text.h")]
     return any(os.path.getmtime(s) > t for s in srcs)
 
 

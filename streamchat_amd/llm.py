@@ -84,6 +84,17 @@ def check_batch_kv_cache(v):
 DEFAULT_BATCH_KV_CACHE = check_batch_kv_cache(os.environ.get("SC_BATCH_KV_CACHE") or "fp16")
 
 
+def check_batch_decode_weights(v):
+    if v not in DECODE_WEIGHTS:
+        raise ValueError(f"batch_decode_weights must be one of {DECODE_WEIGHTS}, got {v!r}")
+    return v
+
+
+# SC_BATCH_DECODE_WEIGHTS=fp8: what Qwen2Model(batch_decode_weights=None) means in this process - the weight format of the BatchDecoders built on
+# the model (chunk captions, beam search).  Read once; the constructor argument wins.  Deliberately independent of SC_DECODE_WEIGHTS.
+DEFAULT_BATCH_DECODE_WEIGHTS = check_batch_decode_weights(os.environ.get("SC_BATCH_DECODE_WEIGHTS") or "fp16")
+
+
 # a layer's decode projections and, in Qwen2Model.w8["L"][l], the key of each one's per-row scales
 _W8_SCALES = dict(wq="sq", wkv="skv", wo="so", wgu="sgu", wd="sd")
 
@@ -94,6 +105,12 @@ def _gemv(P, x, bias=None, **kw):
     return ops.gemv(w, x, bias, **kw) if scale is None else ops.gemv_w8(w, scale, x, bias, **kw)
 
 
+def _gemm(P, a, bias=None, **kw):
+    """ops.gemm from P = (weight, None), ops.gemm_w8 from P = (e4m3 bytes, scales): the projections of BatchDecoder.step"""
+    w, scale = P
+    return ops.gemm(a, w, bias, **kw) if scale is None else ops.gemm_w8(a, w, scale, bias, **kw)
+
+
 def _h(t, device):
     return t.detach().to(device=device, dtype=torch.float16).contiguous()
 
@@ -102,11 +119,12 @@ class Qwen2Model:
     """Decoder stack + lm_head on the HIP kernels, with a contiguous per-layer KV cache [max_seq, 2*Hkv*Dh] (K | V)."""
 
     def __init__(self, state_dict, cfg: Qwen2ConfigLite, device="cuda", max_seq=65536, consume=False, trim_last_layer=True, decode_weights=None, kv_cache=None,
-                 batch_kv_cache=None):
+                 batch_kv_cache=None, batch_decode_weights=None):
         self.cfg, self.device, self.max_seq = cfg, torch.device(device), max_seq
         self.kv_cache, self.kv8, self._kv_stage = "fp16", None, None
         self.set_kv_cache(kv_cache if kv_cache is not None else DEFAULT_KV_CACHE)
         self.set_batch_kv_cache(batch_kv_cache if batch_kv_cache is not None else DEFAULT_BATCH_KV_CACHE)
+        self.set_batch_decode_weights(batch_decode_weights if batch_decode_weights is not None else DEFAULT_BATCH_DECODE_WEIGHTS)
         decode_weights = check_decode_weights(decode_weights if decode_weights is not None else DEFAULT_DECODE_WEIGHTS)
         self.w8 = None                              # enable_fp8_decode(): the e4m3 copies of the decode projections THIS object decodes from
         self._w8_shared = {}                        # ... which every shared_view() of these weights shares (quantised once, whoever asks first)
@@ -149,14 +167,19 @@ class Qwen2Model:
         """Batch-1 decode (`_decode_one`, `DecodeGraph`) from per-output-row FP8 (OCP e4m3fn) copies of wqkv, wo, wgu, wd and lm_head: half
         the weight bytes per token.  OPT-IN, because it is an accuracy trade: about 2.6 % relative rms error on N(0, 0.02^2) weights and on a
         K = 3584 projection's output; the kernels themselves are exact against the dequantised weights (gemv_w8.hip).  The weights are
-        quantised once, here (ops.quantize_rows_e4m3), and kept NEXT TO the fp16 tensors - prefill, BatchDecoder and the token gather of
-        tied embeddings keep using fp16 - which costs about 7.1 GB of device memory at Qwen2-7B's widths.  The switch is per object: a
+        quantised once, here (ops.quantize_rows_e4m3), and kept NEXT TO the fp16 tensors - prefill, the token gather of tied embeddings and - unless asked: set_batch_decode_weights -
+        BatchDecoder keep using fp16 - which costs about 7.1 GB of device memory at Qwen2-7B's widths.  The switch is per object: a
         `shared_view()` of an fp8 model decodes from fp8, a view that enables it leaves its siblings on fp16; the fp8 tensors are shared
         either way (quantised once).  Enable it before the first generate: a DecodeGraph captured earlier keeps the weights it was captured
         with.  Also: Qwen2Model(..., decode_weights="fp8"), SC_DECODE_WEIGHTS=fp8."""
+        self.w8 = self._w8_tensors()
+        return self
+
+    def _w8_tensors(self):
+        """the e4m3 copies of wqkv, wo, wgu, wd and lm_head with their per-row scales, ONE set per weight set: quantised by whoever asks first
+        (enable_fp8_decode, or a BatchDecoder with fp8 weights - which does not switch this object's own batch-1 decode: `w8` stays as it is)"""
         if "w8" in self._w8_shared:
-            self.w8 = self._w8_shared["w8"]
-            return self
+            return self._w8_shared["w8"]
         dq_ = self.cfg.heads * self.cfg.head_dim
         layers = []
         for L in self.L:
@@ -164,8 +187,8 @@ class Qwen2Model:
             # q | k | v quantised as ONE buffer; wq / wkv are row views of the bytes and of the scales, as the fp16 ones are of wqkv
             layers.append(dict(wqkv=qkv, sqkv=sqkv, wq=qkv[:dq_], sq=sqkv[:dq_], wkv=qkv[dq_:], skv=sqkv[dq_:], wo=wo, so=so, wgu=wgu, sgu=sgu, wd=wd, sd=sd))
         head, shead = ops.quantize_rows_e4m3(self.lm_head)
-        self.w8 = self._w8_shared["w8"] = dict(L=layers, lm_head=head, slm_head=shead)
-        return self
+        self._w8_shared["w8"] = dict(L=layers, lm_head=head, slm_head=shead)
+        return self._w8_shared["w8"]
 
     def set_kv_cache(self, mode):
         """"fp8": the batch-1 KV cache of THIS object as OCP e4m3 bytes with one power-of-two scale per (row, KV head, K or V)
@@ -199,6 +222,17 @@ class Qwen2Model:
         if mode == "fp8" and self.cfg.head_dim != 128:
             raise ValueError(f"batch_kv_cache='fp8' needs head_dim 128, got {self.cfg.head_dim}")
         self.batch_kv_cache = mode
+        return self
+
+    def set_batch_decode_weights(self, mode):
+        """"fp8": BatchDecoders built on this object (the chunk captions of a product step, every beam search) run the five projections of their
+        step - q|k|v, o, gate/up, down, lm_head - from the e4m3 tensors of enable_fp8_decode through ops.gemm_w8 (include/streamchat_hip_w8_batched.h):
+        half of the 14.1 GB of weights a step streams at Qwen2-7B's widths.  OPT-IN, the same accuracy trade (about 2.6 % relative rms error per
+        projection; captions and beams may differ from an fp16 run), and deliberately NOT derived from `w8` / decode_weights: an fp8 batch-1 model's
+        BatchDecoder keeps producing its fp16-weight tokens unless asked, and asking does not switch the batch-1 decode.  Per-sequence prefill and the
+        embedding gather stay fp16.  Independent of batch_kv_cache: all four combinations run.  A shared_view() inherits it;
+        BatchDecoder(decode_weights=...) overrides it per decoder.  Also: Qwen2Model(..., batch_decode_weights="fp8"), SC_BATCH_DECODE_WEIGHTS=fp8."""
+        self.batch_decode_weights = check_batch_decode_weights(mode)
         return self
 
     def embed_tokens(self, ids):
@@ -701,15 +735,21 @@ class BatchDecoder:
 
     The caches are this object's own: fp16 `self.cache[l]` [B, cap, 2*dkv], or with kv_cache="fp8" `self.kv8[l]` = (e4m3 bytes uint8 [B, cap, 2*dkv],
     scales fp32 [B, cap, 2*Hkv]) in the format of Qwen2Model.set_kv_cache - the step then appends with ops.kv8_rope_qkv_rows and attends with
-    ops.attention_kv8_batched, everything else is the one body.  An accuracy trade, so opt-in: see Qwen2Model.set_batch_kv_cache."""
+    ops.attention_kv8_batched, everything else is the one body.  An accuracy trade, so opt-in: see Qwen2Model.set_batch_kv_cache.
 
-    kv_cache, kv8 = "fp16", None        # (class defaults: the mode of an object that __init__ has not set up, as tests/_attn_cases.py builds one)
+    The weights of the step's five projections are the model's fp16 tensors, or with decode_weights="fp8" the model's shared e4m3 tensors through
+    ops.gemm_w8 (`_proj` / `_gemm`): the second, independent opt-in, see Qwen2Model.set_batch_decode_weights."""
 
-    def __init__(self, lm, prompts, max_new_tokens, replicate=None, kv_cache=None):
+    kv_cache, kv8, decode_weights, _w8 = "fp16", None, "fp16", None        # (class defaults: the mode of an object that __init__ has not set up, as tests/_attn_cases.py builds one)
+
+    def __init__(self, lm, prompts, max_new_tokens, replicate=None, kv_cache=None, decode_weights=None):
         """prompts: list of [n_b, H] fp16 embeddings (image rows already spliced).  `replicate=N` (beam search): ONE prompt, prefilled once,
         its cache rows copied into N slots - the N beams of llm.LlavaQwenForCausalLM's beam search start from the same prompt.
-        kv_cache: "fp16" | "fp8", None = lm.batch_kv_cache (NOT lm.kv_cache)."""
+        kv_cache: "fp16" | "fp8", None = lm.batch_kv_cache (NOT lm.kv_cache).
+        decode_weights: "fp16" | "fp8", None = lm.batch_decode_weights (NOT whether lm itself decodes from fp8): the weights `step` projects
+        from; the per-sequence prefill below and the embedding gather are fp16 either way."""
         c = lm.cfg
+        check_batch_decode_weights(decode_weights if decode_weights is not None else lm.batch_decode_weights)      # (a bad value raises before any allocation)
         self.kv_cache = check_batch_kv_cache(kv_cache if kv_cache is not None else lm.batch_kv_cache)
         if self.kv_cache == "fp8" and c.head_dim != 128:
             raise ValueError(f"BatchDecoder(kv_cache='fp8') needs head_dim 128, got {c.head_dim}")
@@ -721,6 +761,7 @@ class BatchDecoder:
         else:
             prompts_all = prompts
         self.lm, self.B = lm, len(prompts_all)
+        self.set_decode_weights(decode_weights if decode_weights is not None else lm.batch_decode_weights)      # (lm.w8 is left as it is)
         self.cap = max(int(e.shape[0]) for e in prompts_all) + max_new_tokens
         dev = lm.device
         self._rope_tabs = lm.rope_tabs(self.cap)                 # rotary tables cover every position of this batch before a step is captured; the
@@ -768,6 +809,23 @@ class BatchDecoder:
         """every [B, cap, *] tensor that holds rows of the sequences: the fp16 caches, or the e4m3 bytes and their scales"""
         return self.cache if self.kv_cache != "fp8" else [t for pair in self.kv8 for t in pair]
 
+    def set_decode_weights(self, mode):
+        """switch the weights `step` projects from ("fp16" | "fp8"; the e4m3 tensors are quantised on first use).  Takes effect at the next step
+        or capture: a graph captured earlier keeps the weights it was captured with."""
+        self.decode_weights = check_batch_decode_weights(mode)
+        self._w8 = self.lm._w8_tensors() if self.decode_weights == "fp8" else None
+        return self
+
+    def _proj(self, l):
+        """layer l's projections (l None: lm_head) as name -> (weight, scale or None) for `_gemm`: the model's fp16 tensors, or this decoder's
+        e4m3 bytes with their per-row scales (biases and norm weights are the fp16 ones either way)"""
+        lm, Q = self.lm, self._w8
+        if l is None:
+            return (lm.lm_head, None) if Q is None else (Q["lm_head"], Q["slm_head"])
+        if Q is None:
+            return {k: (lm.L[l][k], None) for k in ("wqkv", "wo", "wgu", "wd")}
+        return dict(wqkv=(Q["L"][l]["wqkv"], Q["L"][l]["sqkv"]), **{k: (Q["L"][l][k], Q["L"][l][_W8_SCALES[k]]) for k in ("wo", "wgu", "wd")})
+
     def step(self, tokens):
         """tokens [B] int32 (device) -> logits [B, vocab] fp32 for the next position of every sequence.  Everything that changes from
         step to step (tokens, lengths, cache rows) lives in device tensors, so the step is hipGraph-capturable."""
@@ -780,7 +838,8 @@ class BatchDecoder:
             # q | k | v in ONE projection launch over the fused weight (the same column sums as two launches), fp32 sums -> RoPE at each
             # sequence's position -> one rounding (the numerics of Qwen2Model._qkv_rows) and the new K | V row appended to each sequence's
             # cache, in ONE launch (round 5: was rope(q) + rope(k|v) + index_copy_)
-            s32 = ops.gemm(x, L["wqkv"], L["bqkv"], out=self._qkv32, out_f32=True)
+            P = self._proj(l)
+            s32 = _gemm(P["wqkv"], x, L["bqkv"], out=self._qkv32, out_f32=True)
             tq, tk = self._rope_tabs
             # the G query heads of a KV group as G query ROWS of that KV head (addressing only; q batch stride = dq)
             G = c.heads // c.kv_heads
@@ -795,11 +854,11 @@ class BatchDecoder:
                 att = ops.attention(q.as_strided((B, G, Dh), (dq, Dh, 1)), ck[:, :, :dkv], ck[:, :, dkv:], c.kv_heads, c.kv_heads, Dh, Dh ** -0.5,
                                     causal=False, kv_len=kvlen, nsplit=self.nsplit, q_head_stride=G * Dh, o_head_stride=G * Dh, out_ld=Dh,
                                     ws=self._ws_attn, q_prescaled=True).view(B, dq)
-            h2 = ops.gemm(att, L["wo"], None, residual=h)
-            m = ops.gemm(ops.rmsnorm(h2, L["ln2"], c.eps), L["wgu"], None, epilogue="swiglu")
-            h = ops.gemm(m, L["wd"], None, residual=h2)
+            h2 = _gemm(P["wo"], att, None, residual=h)
+            m = _gemm(P["wgu"], ops.rmsnorm(h2, L["ln2"], c.eps), None, epilogue="swiglu")
+            h = _gemm(P["wd"], m, None, residual=h2)
         self.len += 1
-        return ops.gemm(ops.rmsnorm(h, lm.norm, c.eps), lm.lm_head, None, out_f32=True)
+        return _gemm(self._proj(None), ops.rmsnorm(h, lm.norm, c.eps), None, out_f32=True)
 
     def prepare_steps(self, max_new_tokens):
         """what `step()` needs when it is driven from outside `generate()` (beam search): the split-KV factor and its workspace"""

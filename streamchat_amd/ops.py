@@ -845,6 +845,41 @@ def gemv_w8(q, scale, x, bias=None, residual=None, epilogue: str = "none", out=N
     return out
 
 
+def gemm_w8(a, q, scale, bias=None, residual=None, epilogue: str = "none", out=None, out_f32: bool = False):
+    """`gemm` for few rows with e4m3 weight bytes and per-row scales (quantize_rows_e4m3):
+    out[M, N] = epi(scale[n] * (a[M, K] @ q[N, K]^T) + bias) (+ residual) - the projections of the batched decode step with half the weight
+    bytes (include/streamchat_hip_w8_batched.h).  epilogue "none" or "swiglu".  A launch serves at most 32 rows; for M > 32 this launches row
+    blocks of 32, and EACH BLOCK RE-READS THE WEIGHTS (a row's bits depend on that row of `a` alone, so they are those of any other
+    blocking) - the kernel is built for the decode batch, not as a general GEMM."""
+    _require_cuda(a, q, scale)
+    _w8_operands(q, scale, "gemm_w8")
+    lib = _lib.load()
+    if a.dtype != torch.float16 or a.dim() != 2 or a.stride(1) != 1 or not q.is_contiguous() or a.shape[1] != q.shape[1]:
+        raise StreamChatHipError("gemm_w8: a must be fp16 [M, K] with unit column stride, q dense [N, K]")
+    if epilogue not in ("none", "swiglu"):
+        raise StreamChatHipError(f"gemm_w8: epilogue {epilogue!r} is not built (none, swiglu)")
+    M, K = a.shape
+    N = q.shape[0]
+    if out is None:
+        out = torch.empty((M, N // 2 if epilogue == "swiglu" else N), dtype=torch.float32 if out_f32 else torch.float16, device=a.device)
+    n_out = N // 2 if epilogue == "swiglu" else N
+    if out.dim() != 2 or out.shape != (M, n_out) or out.dtype not in (torch.float16, torch.float32) or out.device != a.device or out.stride(1) != 1:
+        raise StreamChatHipError(f"gemm_w8: out must be a row-major fp16 or fp32 [{M}, {n_out}] tensor on {a.device}")
+    if bias is not None and (bias.dtype != torch.float16 or bias.shape != (N,) or bias.device != a.device or not bias.is_contiguous()):
+        raise StreamChatHipError(f"gemm_w8: bias must be a contiguous fp16 [{N}] tensor on {a.device}")
+    if residual is not None and (residual.dtype != torch.float16 or residual.shape != (M, N) or residual.device != a.device or residual.stride(1) != 1):
+        raise StreamChatHipError(f"gemm_w8: residual must be a row-major fp16 [{M}, {N}] tensor on {a.device}")
+    from ctypes import c_void_p
+    P = lambda t: None if t is None else c_void_p(t.data_ptr())
+    with torch.cuda.device(a.device), _timed("k_gemm_w8", 2.0 * M * N * K):
+        for r0 in range(0, M, 32):
+            r1 = min(M, r0 + 32)
+            res = None if residual is None else residual[r0:r1]
+            check(lib.sc_gemm_w8_f16(P(a[r0:r1]), a.stride(0), ptr(q), ptr(scale), P(bias), P(res), 0 if res is None else residual.stride(0), P(out[r0:r1]),
+                                     out.stride(0), r1 - r0, N, K, EPI[epilogue], 1 if out.dtype == torch.float32 else 0, stream_ptr(a.device)), "sc_gemm_w8_f16")
+    return out
+
+
 def decode_qkv_tab_w8(wq, sq, wkv, skv, bq, bkv, x, rms_gamma, rms_eps: float, q_out, cache, row_index, q_heads: int, kv_heads: int, Dh: int, tab_q, tab_k):
     """`decode_qkv_tab` with e4m3 weight bytes and per-row scales.  Bit-identical to gemv_w8(out_f32) + rope_f32in."""
     _require_cuda(wq, sq, wkv, skv, x, q_out, cache, row_index, tab_q, tab_k)
